@@ -18,6 +18,10 @@ Contract: ``python bench.py --gpus N --steps K --warmup W``; for N > 1 launched 
 ``torch.distributed.run`` (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from env). W untimed
 warmup steps, then EXACTLY K timed steps bracketed by barrier + device sync on
 both sides; the max over ranks is reported; rank 0 prints ONE JSON line.
+A plain run does only that. ``--full`` adds the side measurements after the timed
+steps (``calibration``, ``busbw_GBps`` at N > 1); ``--dump-outputs DIR`` writes the
+state the last timed step left as ``DIR/<name>.npy`` (same arguments -> same inputs,
+so two builds can be compared array for array).
 
 Every timed step does the full work: batch gather + augmentation on device,
 forward, loss, backward, gradient all-reduce (N > 1), SGD update.
@@ -66,7 +70,7 @@ def parse(argv=None):
                         "rank); torch = torch.distributed; staged = the native C++ step over a gloo process group "
                         "with host staging (several ranks may share one GPU: the N > 1 code path on a 1-GPU box)")
     p.add_argument("--busbw-iters", type=int, default=10,
-                   help="N > 1: all-reduce timings per bucket size after the timed steps (0 = skip)")
+                   help="--full at N > 1: all-reduce timings per bucket size after the timed steps (0 = skip)")
     p.add_argument("--bucket-mb", type=float, default=4.0,
                    help="DDP bucket cap; buckets close at layer boundaries (VGG-11: 9|9|9|4.5|3.7 MiB)")
     p.add_argument("--bucket-policy", type=str, default="layer", choices=["size", "layer", "single"])
@@ -77,6 +81,14 @@ def parse(argv=None):
     p.add_argument("--no-graph", action="store_true", help="native engine: same as --graph none")
     p.add_argument("--graph", type=str, default="auto", choices=["auto", "full", "segments", "none"])
     p.add_argument("--json-out", type=str, default=None)
+    p.add_argument("--full", action="store_true",
+                   help="also take the side measurements that are not part of the headline figure, after the timed "
+                        "steps: the `calibration` block (clock levels, MFMA micro-GEMM) and, at N > 1, the "
+                        "all-reduce bus bandwidth per bucket size (`busbw_GBps`)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step left (loss, parameters, BatchNorm "
+                        "buffers, gradients, momentum) as DIR/<name>.npy, float32, at most 64 MB in all (arrays over "
+                        "their share are a fixed seeded sample); rank 0 writes")
     p.add_argument("--watchdog-s", type=float, default=600.0,
                    help="abort the communicator and exit(18) if one step stalls this long (0 = off)")
     p.add_argument("--comm-probe", type=str, default=None,
@@ -252,6 +264,53 @@ def measure_busbw(trainer, world: int, device, iters: int = 10, warm: int = 3) -
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def _sampled(tensors, budget: int, seed: int):
+    """The tensors flattened into one float32 CPU array; over `budget` elements, a fixed sample
+    instead: the same seeded positions of every tensor on every run, each tensor by its share."""
+    tensors = [t.detach() for t in tensors]
+    total = sum(t.numel() for t in tensors)
+    if total <= budget:
+        return torch.cat([t.reshape(-1).float().cpu() for t in tensors]) if tensors else torch.zeros(0)
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    parts = []
+    for t in tensors:
+        k = max(1, t.numel() * budget // total)
+        idx = torch.randint(0, t.numel(), (k,), generator=g).sort().values
+        parts.append(t.reshape(-1)[idx.to(t.device)].float().cpu())
+    return torch.cat(parts)
+
+
+def dump_outputs(trainer, out_dir: str) -> dict:
+    """Write the state the last timed step left, as a caller of ``trainer.step()`` reads it back:
+    the loss, the updated parameters (and BatchNorm buffers), the gradients and the momentum.
+    One float32 ``<name>.npy`` per array, DUMP_BUDGET_BYTES in all. Returns {name: element count}."""
+    import numpy as np
+    budget = DUMP_BUDGET_BYTES // 4
+    big, small = budget * 3 // 4, budget // 16
+    arrays = {"loss": torch.tensor([trainer.last_loss()], dtype=torch.float32)}
+    if hasattr(trainer, "layout"):  # native engine: the flat buffers (padding included, it stays zero)
+        trainer._join_lag()
+        torch.cuda.synchronize()
+        arrays["params"] = _sampled([trainer.params], big, 1)
+        arrays["bn_buffers"] = _sampled([trainer.bufs], small, 2)
+        arrays["grads"] = _sampled([trainer.grads], small, 3)
+        arrays["momentum"] = _sampled([trainer.mom], small, 4)
+    else:
+        torch.cuda.synchronize()
+        named = list(trainer.module.named_parameters())
+        arrays["params"] = _sampled([p for _, p in named], big, 1)
+        arrays["bn_buffers"] = _sampled([b for _, b in trainer.module.named_buffers() if b.is_floating_point()],
+                                        small, 2)
+        arrays["grads"] = _sampled([p.grad for _, p in named if p.grad is not None], small, 3)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy().astype(np.float32, copy=False))
+    return {name: int(t.numel()) for name, t in arrays.items()}
+
+
 def main(argv=None) -> int:
     args = parse(argv)
     if args.batch_size is None:
@@ -328,9 +387,12 @@ def main(argv=None) -> int:
     if hasattr(trainer, "check_comm"):
         trainer.check_comm()  # async RCCL errors surface here instead of as a silent bad number
     elapsed = D.all_reduce_scalar(elapsed, op=D.ReduceOp.MAX) if world > 1 else elapsed
-    # after the timed window (it never changes `value`): all-reduce bus bandwidth per gradient-bucket
-    # size on the communicator the steps used — BASELINE.json's metric also names it
-    busbw = measure_busbw(trainer, world, device, args.busbw_iters) if world > 1 and args.busbw_iters > 0 else None
+    # before anything below runs further work: the state the last timed step left
+    dumped = dump_outputs(trainer, args.dump_outputs) if args.dump_outputs and rank == 0 else None
+    # --full, after the timed window (it never changes `value`): all-reduce bus bandwidth per gradient-
+    # bucket size on the communicator the steps used — BASELINE.json's metric also names it
+    busbw = measure_busbw(trainer, world, device, args.busbw_iters) \
+        if args.full and world > 1 and args.busbw_iters > 0 else None
     comm_used = comm_kind(trainer, world)
     loss = trainer.last_loss()
     metric, unit, gbatch, seq, baseline, data = describe(args, trainer, world)
@@ -378,7 +440,9 @@ def main(argv=None) -> int:
         out["config"]["comm_defer"] = getattr(trainer, "comm_defer", None)
         out["config"]["wgrad_side_stream"] = getattr(trainer, "overlap_wgrad", None)
     out["config"]["grad_comm_dtype"] = getattr(trainer, "grad_comm_dtype", "fp32")
-    if os.environ.get("CS744_BENCH_CALIBRATE", "1") != "0":
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    if args.full and os.environ.get("CS744_BENCH_CALIBRATE", "1") != "0":
         out["calibration"] = calibration(device)
     if args.phases > 0 and hasattr(trainer, "phase_breakdown"):
         ph = trainer.phase_breakdown(args.phases)

@@ -20,7 +20,8 @@ def main():
     a = p.parse_args()
     for r in range(a.rounds):
         for steps, warm in CONFIGS:
-            out = subprocess.run([sys.executable, "bench.py", "--steps", str(steps), "--warmup", str(warm)], cwd=ROOT,
+            # --full: the calibration block (sclk_mhz below) is not part of a plain run
+            out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", str(steps), "--warmup", str(warm)], cwd=ROOT,
                                  capture_output=True, text=True, timeout=300)
             if out.returncode != 0:
                 print(out.stderr[-2000:], file=sys.stderr)

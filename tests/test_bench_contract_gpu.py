@@ -13,11 +13,12 @@ pytestmark = [pytest.mark.gpu]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_bench_json_line():
+def test_bench_json_line(tmp_path):
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "7", "--warmup", "3"], cwd=ROOT, capture_output=True,
-                       text=True, timeout=240)
+    dump = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3",
+                        "--dump-outputs", str(dump)], cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-1500:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -33,6 +34,16 @@ def test_bench_json_line():
     assert c["model"] == "VGG11" and c["global_batch"] == 64 and c["parallelism"] == "dp1" and c["seq_len"] is None
     assert d["value"] > 0 and abs(d["value"] - 64 * 1e3 / d["ms_per_step"]) / d["value"] < 1e-3
     assert d["vs_baseline"] == pytest.approx(d["value"] / 554.0, rel=1e-2)
+    # a plain run takes no side measurement (those are --full's)
+    assert "calibration" not in d and "busbw_GBps" not in d
+    # --dump-outputs: the state the 10th step left, float32, within the 64 MB budget
+    import numpy as np
+    arrays = {f[:-4]: np.load(dump / f) for f in sorted(os.listdir(dump))}
+    assert set(arrays) == {"loss", "params", "bn_buffers", "grads", "momentum"} == set(d["dumped_outputs"])
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 2 ** 20
+    assert arrays["loss"][0] == pytest.approx(c["final_loss"], abs=1e-4)
+    assert arrays["params"].size > 9_000_000 and np.abs(arrays["grads"]).max() > 0  # all of VGG-11
 
 
 def test_bench_two_ranks_staged_json_line():
@@ -43,7 +54,7 @@ def test_bench_two_ranks_staged_json_line():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     from conftest import torchrun_cmd
-    cmd = torchrun_cmd(2) + ["bench.py", "--gpus", "2",
+    cmd = torchrun_cmd(2) + ["bench.py", "--gpus", "2", "--full",
            "--comm", "staged", "--steps", "5", "--warmup", "2", "--busbw-iters", "3"]
     env = dict(os.environ, CS744_BENCH_CALIBRATE="0")
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300, env=env)
