@@ -197,7 +197,7 @@ class _LinearShadow(torch.autograd.Function):
 class ShadowLinear(torch.nn.Linear):
     """``nn.Linear`` (same parameters and state_dict) whose bf16-autocast forward reads a bf16 copy
     of the fp32 weight kept alongside it instead of casting the weight at every use. ``FusedSGD``
-    rewrites the copy in its update pass (``sgd_multi`` shadow column), so a training step spends no
+    rewrites the copy in its update pass (``sgd_multi`` shadow column; ``FusedAdamW`` does the same), so a training step spends no
     cast kernel on the weights at all, and the weight gradient leaves the GEMM in fp32 (no bf16
     round trip, no cast back). Any other in-place change of the weight (load_state_dict, a DDP
     broadcast, another optimizer) bumps its version and the copy is re-made on the next forward."""

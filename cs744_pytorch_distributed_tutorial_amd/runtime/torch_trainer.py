@@ -7,7 +7,9 @@ framework's own data-parallel runtime around them.
   autograd is still producing earlier layers' gradients) over the native
   ``RcclComm`` (``comm="rccl"``) or ProcessGroupNCCL (``comm="torch"``);
   or any explicit strategy of ``parallel.sync`` (part2a / part2a_extra / part2b);
-* optimizer = ``ops.optim.FusedSGD`` (one multi-tensor HIP launch per step);
+* optimizer = ``ops.optim.FusedSGD`` (one multi-tensor HIP launch per step), or with
+  ``optimizer="adamw"`` / ``CS744_OPTIMIZER=adamw`` ``ops.optim.FusedAdamW`` (AdamW + global-norm
+  gradient clipping: one norm launch, one update launch per parameter group);
 * ResNets run the framework's channels-last path by default (``models.resnet`` ``layout="nhwc"``:
   hipBLASLt GEMM convolutions over gfx950 im2col / BatchNorm / pool kernels, no MIOpen);
   ``CS744_RESNET_LAYOUT=nchw`` selects MIOpen convolutions on NCHW with the fused NCHW
@@ -80,8 +82,16 @@ class TorchTrainer:
     def __init__(self, model: str, batch_size: int, device, rank: int = 0, world: int = 1, sync: str = "ddp",
                  comm: str = "rccl", bucket_mb: float = 25.0, bucket_policy: str = "layer", dtype: str = "fp32",
                  lr: float = 0.1, momentum: float = 0.9, weight_decay: float = 1e-4, seed: int = 5000,
-                 seq_len: int = 0, fused_sgd: bool = True):
-        from ..ops.optim import FusedSGD
+                 seq_len: int = 0, fused_sgd: bool = True, optimizer: Optional[str] = None, betas=(0.9, 0.95),
+                 eps: float = 1e-8, max_grad_norm: Optional[float] = None):
+        """``optimizer``: ``"sgd"`` (momentum SGD, the default) or ``"adamw"`` (AdamW with decoupled weight
+        decay on the parameters with ``dim() >= 2`` only, and global-norm gradient clipping at
+        ``max_grad_norm`` when that is set). ``None`` takes ``CS744_OPTIMIZER`` if set, else ``"sgd"``;
+        only when that variable is set do ``CS744_LR``, ``CS744_WEIGHT_DECAY`` and
+        ``CS744_MAX_GRAD_NORM`` replace ``lr``, ``weight_decay`` and ``max_grad_norm``. ``lr`` and
+        ``weight_decay`` are used as passed for either optimizer: their defaults (0.1, 1e-4) are SGD's
+        and no AdamW setting (a decoder LM wants about ``lr=3e-4, weight_decay=0.1``). ``fused_sgd``
+        means "use the fused optimizer" for both (``FusedSGD`` / ``FusedAdamW`` on a GPU)."""
         torch.manual_seed(seed)
         # MIOpen find mode for the CNN convolutions (CS744_CONV_BENCHMARK=1): time every solver
         # once per shape instead of taking the heuristic pick (opt-in: for ResNet-50 the search ran
@@ -110,9 +120,36 @@ class TorchTrainer:
         else:
             self.net = self.module
             self.sync = make_sync(sync if world > 1 else "none", self.module.parameters())
-        params = self.net.parameters()
-        self.opt = FusedSGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay) if fused_sgd and \
-            torch.cuda.is_available() else torch.optim.SGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay)
+        if optimizer is None and "CS744_OPTIMIZER" in os.environ:
+            optimizer = os.environ["CS744_OPTIMIZER"].lower()
+            lr = float(os.environ.get("CS744_LR", lr))
+            weight_decay = float(os.environ.get("CS744_WEIGHT_DECAY", weight_decay))
+            if "CS744_MAX_GRAD_NORM" in os.environ:
+                max_grad_norm = float(os.environ["CS744_MAX_GRAD_NORM"])
+        optimizer = "sgd" if optimizer is None else optimizer
+        if optimizer not in ("sgd", "adamw"):
+            raise ValueError(f"unknown optimizer {optimizer!r} (sgd or adamw)")
+        self.optimizer = optimizer
+        fused = fused_sgd and torch.cuda.is_available()
+        # clipping done here with clip_grad_norm_ (FusedAdamW clips inside its own pass instead)
+        self.clip_norm = max_grad_norm
+        if optimizer == "adamw":
+            from ..ops.optim import FusedAdamW
+            named = list(self.net.parameters())
+            groups = [{"params": [p for p in named if p.dim() >= 2], "weight_decay": weight_decay},
+                      {"params": [p for p in named if p.dim() < 2], "weight_decay": 0.0}]
+            groups = [g for g in groups if g["params"]]
+            if fused:
+                self.opt = FusedAdamW(groups, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                      max_grad_norm=max_grad_norm)
+                self.clip_norm = None
+            else:
+                self.opt = torch.optim.AdamW(groups, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        else:
+            from ..ops.optim import FusedSGD
+            params = self.net.parameters()
+            self.opt = FusedSGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay) if fused else \
+                torch.optim.SGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay)
         self.crit = nn.CrossEntropyLoss()
         if self.is_lm:
             self.data = SyntheticBatches("tokens", batch_size, device, seq=seq_len or self.module.max_seq,
@@ -141,6 +178,9 @@ class TorchTrainer:
         with roctx_range("cs.sync"):
             self.sync()
         with roctx_range("cs.sgd"):
+            if self.clip_norm is not None:
+                torch.nn.utils.clip_grad_norm_([p for g in self.opt.param_groups for p in g["params"]],
+                                               self.clip_norm)
             self.opt.step()
         self.loss = loss.detach()
 

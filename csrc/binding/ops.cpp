@@ -98,6 +98,113 @@ void sgd_multi(torch::Tensor table, int64_t ntens, int64_t nchunks, double lr, d
                          (float)lr, (float)mom, (float)wd, (float)damp, (float)scale, first ? 1 : 0, cur_stream()));
 }
 
+// The AdamW table: {p, g, exp_avg, exp_avg_sq, n, shadow, flags} per tensor + chunk prefix, built once
+// per distinct pointer set. Layout: [ntens*7 entries | ntens chunk starts | nchunks]. The same host
+// checks as sgd_multi_table; flags record which entries allow 16-byte vector access (a parameter that
+// is a view at an odd offset takes the scalar loop).
+torch::Tensor adamw_multi_table(std::vector<torch::Tensor> ps, std::vector<torch::Tensor> gs,
+                                std::vector<torch::Tensor> ms, std::vector<torch::Tensor> vs,
+                                c10::optional<std::vector<torch::Tensor>> shadows) {
+  TORCH_CHECK(ps.size() == gs.size() && ps.size() == ms.size() && ps.size() == vs.size() && !ps.empty(),
+              "adamw_multi_table: the param, grad, exp_avg and exp_avg_sq lists must be non-empty and equally long");
+  TORCH_CHECK(!shadows.has_value() || shadows->size() == ps.size(), "adamw_multi_table: shadow list size");
+  static_assert(sizeof(CsAdamEntry) == 7 * sizeof(int64_t), "CsAdamEntry: seven 8-byte fields");
+  const int64_t nt = ps.size();
+  auto host = torch::empty({nt * 7 + nt + 1}, torch::kLong);
+  int64_t* h = host.data_ptr<int64_t>();
+  int64_t chunks = 0;
+  for (int64_t i = 0; i < nt; ++i) {
+    for (auto* t : {&ps[i], &gs[i], &ms[i], &vs[i]}) {
+      TORCH_CHECK(t->is_cuda(), "adamw_multi_table: every tensor must be on the GPU");
+      TORCH_CHECK(t->device() == ps[0].device(), "adamw_multi_table: every tensor must be on one device");
+      TORCH_CHECK(t->scalar_type() == at::kFloat, "adamw_multi_table: param, grad and state must be float32");
+      TORCH_CHECK(t->is_non_overlapping_and_dense(), "adamw_multi_table: tensors must be dense");
+    }
+    TORCH_CHECK(ps[i].numel() == gs[i].numel() && ps[i].numel() == ms[i].numel() && ps[i].numel() == vs[i].numel(),
+                "adamw_multi_table: param, grad, exp_avg and exp_avg_sq must have one size");
+    TORCH_CHECK(ps[i].strides() == gs[i].strides() && ps[i].strides() == ms[i].strides() &&
+                    ps[i].strides() == vs[i].strides(),
+                "adamw_multi_table: param, grad, exp_avg and exp_avg_sq must share one memory layout");
+    int64_t sh = 0;
+    if (shadows.has_value() && (*shadows)[i].numel() > 0) {
+      const auto& t = (*shadows)[i];
+      TORCH_CHECK(t.is_cuda() && t.device() == ps[0].device(), "adamw_multi_table: a shadow must be on the GPU");
+      TORCH_CHECK(t.scalar_type() == at::kBFloat16 && t.numel() == ps[i].numel() && t.strides() == ps[i].strides(),
+                  "adamw_multi_table: a shadow must be a bf16 tensor laid out like its parameter");
+      sh = (int64_t)t.data_ptr();
+    }
+    int64_t* e = h + i * 7;
+    e[0] = (int64_t)ps[i].data_ptr<float>();
+    e[1] = (int64_t)gs[i].data_ptr<float>();
+    e[2] = (int64_t)ms[i].data_ptr<float>();
+    e[3] = (int64_t)vs[i].data_ptr<float>();
+    e[4] = ps[i].numel();
+    e[5] = sh;
+    const bool vec_g = e[1] % 16 == 0;
+    const bool vec = vec_g && e[0] % 16 == 0 && e[2] % 16 == 0 && e[3] % 16 == 0 && sh % 8 == 0;
+    e[6] = (vec ? CS_ADAM_VEC : 0) | (vec_g ? CS_ADAM_VEC_G : 0);
+    h[nt * 7 + i] = chunks;
+    chunks += (ps[i].numel() + 4095) / 4096;
+  }
+  TORCH_CHECK(chunks < (int64_t)1 << 31, "adamw_multi_table: too many chunks");
+  h[nt * 8] = chunks;
+  return host.to(ps[0].device());
+}
+
+int64_t adam_table_ntens(const torch::Tensor& table, const char* who) {
+  CS_CHECK_CUDA(table);
+  TORCH_CHECK(table.scalar_type() == at::kLong && table.dim() == 1 && table.is_contiguous() &&
+                  table.numel() >= 9 && (table.numel() - 1) % 8 == 0,
+              who, ": not a table of adamw_multi_table");
+  return (table.numel() - 1) / 8;
+}
+
+// partials[b] = block b's sum of (g * grad_scale)^2 over the whole table (double, CS_ADAM_PARTIALS slots)
+void grad_sumsq(torch::Tensor table, int64_t ntens, int64_t nchunks, double grad_scale, torch::Tensor partials) {
+  const int64_t nt = adam_table_ntens(table, "grad_sumsq");
+  TORCH_CHECK(ntens == nt && nchunks >= 1 && nchunks < (int64_t)1 << 31, "grad_sumsq: the norm covers the whole table");
+  CS_CHECK_CUDA(partials);
+  TORCH_CHECK(partials.scalar_type() == at::kDouble && partials.is_contiguous() &&
+                  partials.numel() == CS_ADAM_PARTIALS && partials.device() == table.device(),
+              "grad_sumsq: partials must be ", CS_ADAM_PARTIALS, " float64 values on the table's device");
+  DevGuard gd(table.device());
+  const int64_t* t = table.data_ptr<int64_t>();
+  CS_LAUNCH(cs_grad_sumsq(reinterpret_cast<const CsAdamEntry*>(t), (int)nt, t + nt * 7, (int)nchunks,
+                          (float)grad_scale, partials.data_ptr<double>(), cur_stream()));
+}
+
+// The update of tensors [first_tensor, first_tensor + ntens) of the table (one parameter group), whose
+// chunks are [first_chunk, first_chunk + nchunks). partials + norm_out given: clip by the global norm
+// that grad_sumsq left in partials, and write the norm to norm_out.
+void adamw_multi(torch::Tensor table, int64_t ntens, int64_t nchunks, double lr, double beta1, double beta2,
+                 double eps, double wd, double bc1, double bc2, double grad_scale, double max_norm,
+                 c10::optional<torch::Tensor> partials, c10::optional<torch::Tensor> norm_out, int64_t first_tensor,
+                 int64_t first_chunk) {
+  const int64_t nt = adam_table_ntens(table, "adamw_multi");
+  TORCH_CHECK(first_tensor >= 0 && ntens >= 1 && first_tensor + ntens <= nt, "adamw_multi: tensor range outside the table");
+  TORCH_CHECK(first_chunk >= 0 && nchunks >= 1 && first_chunk + nchunks < (int64_t)1 << 31, "adamw_multi: chunk range");
+  TORCH_CHECK(bc1 > 0 && bc2 > 0, "adamw_multi: bias corrections must be positive (step >= 1, beta < 1)");
+  TORCH_CHECK(partials.has_value() == norm_out.has_value(), "adamw_multi: partials and norm_out go together");
+  const double* pp = nullptr;
+  float* no = nullptr;
+  if (partials.has_value()) {
+    CS_CHECK_CUDA(*partials); CS_CHECK_CUDA(*norm_out);
+    TORCH_CHECK(partials->scalar_type() == at::kDouble && partials->is_contiguous() &&
+                    partials->numel() == CS_ADAM_PARTIALS && partials->device() == table.device(),
+                "adamw_multi: partials must be ", CS_ADAM_PARTIALS, " float64 values on the table's device");
+    TORCH_CHECK(norm_out->scalar_type() == at::kFloat && norm_out->numel() == 1 && norm_out->device() == table.device(),
+                "adamw_multi: norm_out must be one float32 on the table's device");
+    TORCH_CHECK(max_norm > 0, "adamw_multi: max_norm must be positive");
+    pp = partials->data_ptr<double>();
+    no = norm_out->data_ptr<float>();
+  }
+  DevGuard gd(table.device());
+  const int64_t* t = table.data_ptr<int64_t>();
+  CS_LAUNCH(cs_adamw_multi(reinterpret_cast<const CsAdamEntry*>(t) + first_tensor, (int)ntens,
+                           t + nt * 7 + first_tensor, (int)first_chunk, (int)nchunks, lr, beta1, beta2, eps, wd, bc1,
+                           bc2, (float)grad_scale, (float)max_norm, pp, no, cur_stream()));
+}
+
 // part2a root combine: dst[n] = mean over rows of src[rows * n] (rank order)
 // (bcast: the mean is also written over every row of src)
 void rows_mean(torch::Tensor src, int64_t rows, torch::Tensor dst, bool bcast) {
@@ -188,6 +295,17 @@ PYBIND11_MODULE(_C, m) {
   m.def("sgd_multi_table", &sgd_multi_table, "build the multi-tensor SGD table", pybind11::arg("ps"), pybind11::arg("gs"),
         pybind11::arg("ms"), pybind11::arg("shadows") = pybind11::none());
   m.def("sgd_multi", &sgd_multi, "multi-tensor fused SGD");
+  m.def("adamw_multi_table", &adamw_multi_table, "build the multi-tensor AdamW table", pybind11::arg("ps"),
+        pybind11::arg("gs"), pybind11::arg("ms"), pybind11::arg("vs"), pybind11::arg("shadows") = pybind11::none());
+  m.def("grad_sumsq", &grad_sumsq, "per-block sums of (g * grad_scale)^2 over an AdamW table (deterministic)",
+        pybind11::arg("table"), pybind11::arg("ntens"), pybind11::arg("nchunks"), pybind11::arg("grad_scale"),
+        pybind11::arg("partials"));
+  m.def("adamw_multi", &adamw_multi, "multi-tensor fused AdamW, optionally clipped by the global gradient norm",
+        pybind11::arg("table"), pybind11::arg("ntens"), pybind11::arg("nchunks"), pybind11::arg("lr"),
+        pybind11::arg("beta1"), pybind11::arg("beta2"), pybind11::arg("eps"), pybind11::arg("wd"), pybind11::arg("bc1"),
+        pybind11::arg("bc2"), pybind11::arg("grad_scale") = 1.0, pybind11::arg("max_norm") = 0.0,
+        pybind11::arg("partials") = pybind11::none(), pybind11::arg("norm_out") = pybind11::none(),
+        pybind11::arg("first_tensor") = 0, pybind11::arg("first_chunk") = 0);
   m.def("rows_mean", &rows_mean, "mean over the rows of a [rows, n] buffer (part2a root)", pybind11::arg("src"),
         pybind11::arg("rows"), pybind11::arg("dst"), pybind11::arg("bcast") = false);
   m.def("accumulate", &accumulate, "g += t, optionally then g /= div (part2a_extra root)");

@@ -50,6 +50,34 @@ hipError_t cs_cast_grad(const void* src, void* dst, int64_t n, int to_bf16, hipS
 hipError_t cs_sgd_multi(const CsTensorEntry* tab_dev, int ntens, const int64_t* chunk_start_dev, int nchunks,
                         float lr, float mom, float wd, float damp, float scale, int first, hipStream_t stream);
 
+// AdamW with global-norm gradient clipping (adamw.hip): a table of its own, walked in the same
+// 4096-element chunks as cs_sgd_multi (chunk starts as a prefix array over the whole table)
+struct CsAdamEntry {
+  float* p;
+  float* g;
+  float* m;  // exp_avg
+  float* v;  // exp_avg_sq
+  int64_t n;
+  uint16_t* shadow;  // optional bf16 copy of p, rewritten by the update
+  int64_t flags;     // CS_ADAM_VEC: every pointer allows 4-element vector access; CS_ADAM_VEC_G: g does
+};
+#define CS_ADAM_VEC 1
+#define CS_ADAM_VEC_G 2
+#define CS_ADAM_PARTIALS 2048
+// partials[CS_ADAM_PARTIALS] (double): block b's sum of (g * grad_scale)^2 over chunks b, b + grid, ...
+// of the whole table, the slots past the grid zeroed. No atomics: the same table gives the same bits.
+hipError_t cs_grad_sumsq(const CsAdamEntry* tab_dev, int ntens, const int64_t* chunk_start_dev, int nchunks,
+                         float grad_scale, double* partials, hipStream_t stream);
+// The update of the tensors [0, ntens) of tab_dev (a contiguous run of the table: one parameter group),
+// whose chunks are [first_chunk, first_chunk + nchunks) of the table's numbering. partials != nullptr:
+// the gradient is clipped to max_norm by the global norm (torch's clip_grad_norm_ coefficient) and the
+// norm is written to norm_out. bc1 = 1 - beta1^step and bc2 = 1 - beta2^step come from the host; the
+// launcher folds 1 - lr*wd, lr/bc1 and sqrt(bc2) in double and rounds each to float once, as torch does.
+hipError_t cs_adamw_multi(const CsAdamEntry* tab_dev, int ntens, const int64_t* chunk_start_dev, int first_chunk,
+                          int nchunks, double lr, double beta1, double beta2, double eps, double wd, double bc1,
+                          double bc2, float grad_scale, float max_norm, const double* partials, float* norm_out,
+                          hipStream_t stream);
+
 // classifier head
 // bn (optional, part 0 / 1): the features are the last VGG block's BatchNorm + ReLU + 2x2 max-pool of
 // its pre-BN output y [B][2][2][K] (scale / shift per channel), computed in the row pass (bn_apply's
