@@ -4,6 +4,12 @@ D 128, causal, bf16). FLOPs counted as 4*B*Hq*S*S*D (forward, halved for causal)
 that for forward+backward (the backward's five products, 2.5x the forward's two).
 
     python -m cs744_pytorch_distributed_tutorial_amd.bench.attention --seq 2048 4096
+
+``--doc-len N`` packs equal documents of N tokens into every row and adds the document-masked
+kernels (``native_doc_*``): their TFLOP/s count only the visible (query, key) pairs, whose share of
+the causal triangle is ``visible_fraction``.
+
+    python -m cs744_pytorch_distributed_tutorial_amd.bench.attention --seq 8192 --doc-len 1024
 """
 from __future__ import annotations
 
@@ -35,8 +41,9 @@ def main(argv=None) -> None:
     p.add_argument("--kv-heads", type=int, default=8)
     p.add_argument("--head-dim", type=int, default=128)
     p.add_argument("--iters", type=int, default=20)
+    p.add_argument("--doc-len", type=int, default=None, help="also time document-masked attention, documents of N tokens")
     a = p.parse_args(argv)
-    from ..ops.attention import attention
+    from ..ops.attention import attention, doc_bounds
     dev = torch.device("cuda", 0)
     for S in a.seq:
         B, Hq, Hkv, D = a.batch, a.heads, a.kv_heads, a.head_dim
@@ -64,8 +71,26 @@ def main(argv=None) -> None:
             F.scaled_dot_product_attention(qt, kt, vt, is_causal=True, enable_gqa=True).backward(dot)
 
         row = {"B": B, "S": S, "Hq": Hq, "Hkv": Hkv, "D": D}
-        for name, fn, fl in (("native_fwd", ours_f, flops), ("native_fwd_bwd", ours_fb, 3.5 * flops),
-                             ("sdpa_fwd", sdpa_f, flops), ("sdpa_fwd_bwd", sdpa_fb, 3.5 * flops)):
+        arms = [("native_fwd", ours_f, flops), ("native_fwd_bwd", ours_fb, 3.5 * flops),
+                ("sdpa_fwd", sdpa_f, flops), ("sdpa_fwd_bwd", sdpa_fb, 3.5 * flops)]
+        if a.doc_len is not None:
+            N = a.doc_len
+            doc = doc_bounds((torch.arange(S, device=dev) // N).expand(B, S))
+            lens = [min(N, S - s0) for s0 in range(0, S, N)]
+            pairs = sum(n * (n + 1) // 2 for n in lens)  # visible (query, key) pairs of one row
+            dflops = 4.0 * B * Hq * pairs * D
+            row["doc_len"] = N
+            row["visible_fraction"] = round(pairs / (S * (S + 1) // 2), 5)
+
+            def doc_f():
+                with torch.no_grad():
+                    attention(q, k, v, True, doc)
+
+            def doc_fb():
+                attention(q, k, v, True, doc).backward(do)
+
+            arms[2:2] = [("native_doc_fwd", doc_f, dflops), ("native_doc_fwd_bwd", doc_fb, 3.5 * dflops)]
+        for name, fn, fl in arms:
             try:
                 ms = _time(fn, a.iters)
                 row[name + "_ms"] = round(ms, 4)

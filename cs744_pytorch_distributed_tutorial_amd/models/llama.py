@@ -38,13 +38,14 @@ class LlamaConfig:
     max_seq: int = 8192
     rope_theta: float = 500000.0
     norm_eps: float = 1e-5
+    eos_id: int = 128001  # <|end_of_text|> of the Llama-3 vocabulary: closes a document of a packed row
 
 
 CONFIGS = {
     "llama3-8b": LlamaConfig(),
     "llama3-1b": LlamaConfig(dim=2048, n_layers=16, n_heads=32, n_kv_heads=8, ffn_dim=8192, max_seq=2048),
     "llama-tiny": LlamaConfig(dim=256, n_layers=2, n_heads=4, n_kv_heads=2, ffn_dim=512, vocab_size=1024,
-                              max_seq=128),
+                              max_seq=128, eos_id=1023),
 }
 
 
@@ -86,15 +87,18 @@ class Attention(nn.Module):
         self.wv = _Linear(cfg.dim, self.nkv * self.hd, bias=False)
         self.wo = _Linear(self.nh * self.hd, cfg.dim, bias=False)
 
-    def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, doc=None) -> torch.Tensor:
+        """``doc``: ``ops.attention.DocBounds`` of a packed batch (attention stays inside a document)."""
         B, S, _ = x.shape
         q = self.wq(x).view(B, S, self.nh, self.hd)
         k = self.wk(x).view(B, S, self.nkv, self.hd)
         v = self.wv(x).view(B, S, self.nkv, self.hd)
         q, k = _ops().rope(q, cos, sin), _ops().rope(k, cos, sin)
-        from ..ops.attention import attention, native_ok
+        from ..ops.attention import attention, attention_ref, native_ok
         if native_ok(q, k, v):
-            o = attention(q, k, v, causal=True)  # [B, S, Hq, hd], gfx950 flash attention
+            o = attention(q, k, v, causal=True, doc=doc)  # [B, S, Hq, hd], gfx950 flash attention
+        elif doc is not None:  # CPU / fp32 with a document mask: the math reference (masked weights exactly 0)
+            o = attention_ref(q, k, v, True, doc)
         else:  # CPU / fp32: PyTorch's attention
             q, k, v = q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2)
             o = F.scaled_dot_product_attention(q, k, v, is_causal=True, enable_gqa=self.nkv != self.nh).transpose(1, 2)
@@ -120,8 +124,8 @@ class Block(nn.Module):
         self.ffn_norm = RMSNorm(cfg.dim, cfg.norm_eps)
         self.feed_forward = FeedForward(cfg)
 
-    def forward(self, x, cos, sin):
-        x = x + self.attention(self.attention_norm(x), cos, sin)
+    def forward(self, x, cos, sin, doc=None):
+        x = x + self.attention(self.attention_norm(x), cos, sin, doc)
         return x + self.feed_forward(self.ffn_norm(x))
 
 
@@ -150,12 +154,22 @@ class Llama(nn.Module):
             self._rope = rope_tables(max(S, 1), self.cfg.dim // self.cfg.n_heads, self.cfg.rope_theta, device)
         return self._rope[0][:S], self._rope[1][:S]
 
-    def forward(self, tokens: torch.Tensor) -> torch.Tensor:
+    def forward(self, tokens: torch.Tensor, doc_ids: torch.Tensor = None) -> torch.Tensor:
+        """``doc_ids``: integer [B, S], the document of every token of a packed batch
+        (``ops.attention.doc_ids_from_eos``); attention is then confined to a token's own document.
+        RoPE positions are NOT reset per document: a RoPE score depends only on ``i - j``, so inside
+        a document the result is the same as with positions counted from the document's start."""
         S = tokens.shape[1]
         cos, sin = self._tables(S, tokens.device)
         h = self.tok_embeddings(tokens)
-        for blk in self.layers:
-            h = blk(h, cos, sin)
+        if doc_ids is None:
+            for blk in self.layers:
+                h = blk(h, cos, sin)
+        else:
+            from ..ops.attention import doc_bounds
+            doc = doc_bounds(doc_ids)  # once per forward, shared by every layer
+            for blk in self.layers:
+                h = blk(h, cos, sin, doc)
         return self.output(self.norm(h))
 
 

@@ -17,7 +17,9 @@ framework's own data-parallel runtime around them.
   NCHW layout) measured 10-18x SLOWER on MI355X (torch 2.10+rocm7.0: composable_kernel
   weight-gradient kernels up to 225 ms each). Optionally under bf16 autocast
   (``dtype="bf16"``; master weights and the optimizer stay fp32);
-* data = device-resident synthetic batches of the named shape (no host traffic).
+* data = device-resident synthetic batches of the named shape (no host traffic); for the LM,
+  ``doc_len=N`` / ``CS744_DOC_LEN=N`` packs documents of about N tokens into every row and trains
+  with document-masked attention (``ops.attention``), the mask derived from the EOS tokens each step.
 """
 from __future__ import annotations
 
@@ -49,11 +51,15 @@ class SyntheticBatches:
     """A pool of random, fixed, device-resident samples; each step gathers a random batch.
 
     Images: uint8 NHWC pool -> fp32/bf16 normalised NCHW(channels_last) batch.
-    Tokens: int64 [pool, seq+1] -> (input, target) shifted pair.
+    Tokens: int64 [pool, seq+1] -> (input, target) shifted pair. With ``doc_len=N`` every pool row is
+    cut into documents once, here: lengths uniform on [max(1, N // 2), 3 N // 2] from the seeded CPU
+    generator (drawn after the tokens, which stay those of the undivided pool), the last document
+    truncated at the row end, ``eos_id`` written at each document's last position.
     """
 
     def __init__(self, kind: str, batch: int, device, shape=(3, 224, 224), classes: int = 1000, pool: int = 512,
-                 seq: int = 0, vocab: int = 0, seed: int = 0, channels_last: bool = True):
+                 seq: int = 0, vocab: int = 0, seed: int = 0, channels_last: bool = True,
+                 doc_len: Optional[int] = None, eos_id: Optional[int] = None):
         self.fmt = torch.channels_last if channels_last else torch.contiguous_format
         g = torch.Generator(device="cpu").manual_seed(seed)
         self.kind, self.batch, self.device = kind, batch, device
@@ -65,7 +71,16 @@ class SyntheticBatches:
             self.mean = torch.tensor([0.485, 0.456, 0.406], device=device).view(1, 3, 1, 1) * 255
             self.std = torch.tensor([0.229, 0.224, 0.225], device=device).view(1, 3, 1, 1) * 255
         else:
-            self.tokens = torch.randint(0, vocab, (self.pool, seq + 1), generator=g).to(device)
+            tokens = torch.randint(0, vocab, (self.pool, seq + 1), generator=g)
+            if doc_len is not None:
+                if doc_len < 1 or eos_id is None or not 0 <= eos_id < vocab:
+                    raise ValueError("doc_len needs doc_len >= 1 and an eos_id inside the vocabulary")
+                lo, hi, L = max(1, doc_len // 2), 3 * doc_len // 2, seq + 1
+                n = L // lo + 1  # documents that certainly cover a row; the one crossing its end is truncated
+                ends = torch.randint(lo, hi + 1, (self.pool, n), generator=g).cumsum(1) - 1  # last positions
+                eos = torch.zeros(self.pool, L, dtype=torch.bool).scatter_(1, ends.clamp_(max=L - 1), True)
+                tokens = tokens.masked_fill(eos, eos_id)
+            self.tokens = tokens.to(device)
         self.gen = torch.Generator(device=device).manual_seed(seed + 1)
 
     def next(self):
@@ -83,8 +98,13 @@ class TorchTrainer:
                  comm: str = "rccl", bucket_mb: float = 25.0, bucket_policy: str = "layer", dtype: str = "fp32",
                  lr: float = 0.1, momentum: float = 0.9, weight_decay: float = 1e-4, seed: int = 5000,
                  seq_len: int = 0, fused_sgd: bool = True, optimizer: Optional[str] = None, betas=(0.9, 0.95),
-                 eps: float = 1e-8, max_grad_norm: Optional[float] = None):
-        """``optimizer``: ``"sgd"`` (momentum SGD, the default) or ``"adamw"`` (AdamW with decoupled weight
+                 eps: float = 1e-8, max_grad_norm: Optional[float] = None, doc_len: Optional[int] = None):
+        """``doc_len``: pack documents of about that many tokens into every row of the synthetic token
+        pool (``SyntheticBatches``) and train with document-masked attention: ``step()`` derives the
+        document of every token from the EOS tokens of its input, the way real packed data would be
+        handled. ``None`` takes ``CS744_DOC_LEN`` if set, else no document masking. LM models only.
+
+        ``optimizer``: ``"sgd"`` (momentum SGD, the default) or ``"adamw"`` (AdamW with decoupled weight
         decay on the parameters with ``dim() >= 2`` only, and global-norm gradient clipping at
         ``max_grad_norm`` when that is set). ``None`` takes ``CS744_OPTIMIZER`` if set, else ``"sgd"``;
         only when that variable is set do ``CS744_LR``, ``CS744_WEIGHT_DECAY`` and
@@ -151,9 +171,16 @@ class TorchTrainer:
             self.opt = FusedSGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay) if fused else \
                 torch.optim.SGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay)
         self.crit = nn.CrossEntropyLoss()
+        if doc_len is None and "CS744_DOC_LEN" in os.environ:
+            doc_len = int(os.environ["CS744_DOC_LEN"])
+        if doc_len is not None and not self.is_lm:
+            raise ValueError(f"doc_len (document-masked attention) is for the LM models, not {model!r}")
+        self.doc_len = doc_len
         if self.is_lm:
+            self.eos_id = self.module.cfg.eos_id
             self.data = SyntheticBatches("tokens", batch_size, device, seq=seq_len or self.module.max_seq,
-                                         vocab=self.module.vocab_size, seed=seed)
+                                         vocab=self.module.vocab_size, seed=seed, doc_len=doc_len,
+                                         eos_id=self.eos_id if doc_len is not None else None)
         else:
             shape = (3, 32, 32) if model.lower().startswith("vgg") else (3, 224, 224)
             classes = 10 if model.lower().startswith("vgg") else 1000
@@ -167,7 +194,11 @@ class TorchTrainer:
         x, y = self.data.next()
         self.opt.zero_grad()  # DDP re-attaches its bucket views (and zeroes them) in forward
         with roctx_range("cs.forward"), torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.dtype == "bf16"):
-            out = self.net(x)
+            if self.doc_len is not None:  # packed rows: documents end at the EOS tokens of the input
+                from ..ops.attention import doc_ids_from_eos
+                out = self.net(x, doc_ids=doc_ids_from_eos(x, self.eos_id))
+            else:
+                out = self.net(x)
             if self.is_lm:  # fused gfx950 softmax cross-entropy over the bf16 logits (ops.lm)
                 from ..ops.lm import cross_entropy
                 loss = cross_entropy(out.view(-1, out.shape[-1]), y.view(-1))

@@ -123,26 +123,59 @@ void attn_check(const torch::Tensor& q, const torch::Tensor& k, const torch::Ten
   TORCH_CHECK(q.size(2) % k.size(2) == 0, "attention: query heads must be a multiple of kv heads");
 }
 
-std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, double scale, bool causal) {
+// the document mask of a packed batch (ops/attention.py doc_bounds): both arrays or neither
+bool doc_check(const torch::Tensor& q, const c10::optional<torch::Tensor>& kstart,
+               const c10::optional<torch::Tensor>& qend, bool causal) {
+  TORCH_CHECK(kstart.has_value() == qend.has_value(), "attention: kstart and qend must be given together");
+  if (!kstart.has_value()) return false;
+  TORCH_CHECK(causal, "attention: a document mask is defined only together with causal=True");
+  for (auto* t : {&*kstart, &*qend}) {
+    TORCH_CHECK(t->scalar_type() == at::kInt, "attention: kstart / qend must be int32, got ", t->scalar_type());
+    TORCH_CHECK(t->is_cuda() && t->device() == q.device(), "attention: kstart / qend must be on q's device");
+    TORCH_CHECK(t->is_contiguous(), "attention: kstart / qend must be contiguous");
+    TORCH_CHECK(t->dim() == 2 && t->size(0) == q.size(0) && t->size(1) == q.size(1),
+                "attention: kstart / qend must be shaped [B, S] = [", q.size(0), ", ", q.size(1), "]");
+  }
+  return true;
+}
+
+std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, double scale, bool causal,
+                                    c10::optional<torch::Tensor> kstart, c10::optional<torch::Tensor> qend) {
   attn_check(q, k, v);
+  const bool doc = doc_check(q, kstart, qend, causal);
   DevGuard g(q.device());
   auto o = torch::empty_like(q);
   auto lse = torch::empty({q.size(0), q.size(2), q.size(1)}, q.options().dtype(at::kFloat));
+  if (doc) {
+    CS_LAUNCH(cs_attn_fwd_doc(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(), q.size(0),
+                              q.size(1), q.size(2), k.size(2), q.size(3), (float)scale, kstart->data_ptr<int>(),
+                              cur_stream()));
+    return {o, lse};
+  }
   CS_LAUNCH(cs_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(), q.size(0),
                         q.size(1), q.size(2), k.size(2), q.size(3), (float)scale, causal ? 1 : 0, cur_stream()));
   return {o, lse};
 }
 
 std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor o,
-                                    torch::Tensor lse, torch::Tensor dout, double scale, bool causal) {
+                                    torch::Tensor lse, torch::Tensor dout, double scale, bool causal,
+                                    c10::optional<torch::Tensor> kstart, c10::optional<torch::Tensor> qend) {
   attn_check(q, k, v);
   check(o, "o"); check(dout, "dout"); check(lse, "lse");
   TORCH_CHECK(o.sizes() == q.sizes() && dout.sizes() == q.sizes() && o.scalar_type() == at::kBFloat16 &&
                   dout.scalar_type() == at::kBFloat16, "attn_bwd: o / dout must match q");
   TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() == q.size(0) * q.size(2) * q.size(1), "attn_bwd: lse");
+  const bool doc = doc_check(q, kstart, qend, causal);
   DevGuard g(q.device());
   auto dq = torch::empty_like(q), dk = torch::empty_like(k), dv = torch::empty_like(v);
   auto delta = torch::empty_like(lse);
+  if (doc) {
+    CS_LAUNCH(cs_attn_bwd_doc(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), dout.data_ptr(),
+                              lse.data_ptr<float>(), delta.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(),
+                              dv.data_ptr(), q.size(0), q.size(1), q.size(2), k.size(2), q.size(3), (float)scale,
+                              kstart->data_ptr<int>(), qend->data_ptr<int>(), cur_stream()));
+    return {dq, dk, dv};
+  }
   CS_LAUNCH(cs_attn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), dout.data_ptr(), lse.data_ptr<float>(),
                         delta.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), q.size(0), q.size(1),
                         q.size(2), k.size(2), q.size(3), (float)scale, causal ? 1 : 0, cur_stream()));
@@ -242,8 +275,13 @@ void register_lm_ops(pybind11::module& m) {
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("rope", &rope);
-  m.def("attn_fwd", &attn_fwd, "flash attention forward (bf16 [B,S,H,D], GQA, causal)");
-  m.def("attn_bwd", &attn_bwd, "flash attention backward -> dq, dk, dv");
+  namespace py = pybind11;
+  m.def("attn_fwd", &attn_fwd, "flash attention forward (bf16 [B,S,H,D], GQA, causal; kstart / qend: document mask)",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"), py::arg("causal"),
+        py::arg("kstart") = c10::nullopt, py::arg("qend") = c10::nullopt);
+  m.def("attn_bwd", &attn_bwd, "flash attention backward -> dq, dk, dv", py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("o"), py::arg("lse"), py::arg("dout"), py::arg("scale"), py::arg("causal"),
+        py::arg("kstart") = c10::nullopt, py::arg("qend") = c10::nullopt);
   m.def("mm_bf16", &mm_bf16, "C = a @ b on the bf16 matrix cores", pybind11::arg("a"), pybind11::arg("b"),
         pybind11::arg("out_f32") = false, pybind11::arg("acc") = c10::nullopt, pybind11::arg("splits") = -1);
   m.def("mm_bf16_bn_stats", &mm_bf16_bn_stats, "a @ b (bf16) plus per-256-row-tile BatchNorm (mean, M2) of the result");

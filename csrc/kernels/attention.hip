@@ -24,6 +24,8 @@
 //   attn_dkdv:  per 128-key block of one kv head, every query head of its group: S = Q K^T,
 //               dP = dO V^T (key on the lane), dV^T += dO^T P, dK^T += Q^T dS; Q/dO tiles of 64
 //               queries (+ their L2 and delta) double-buffered in LDS.
+// Document mask for packed sequences (causal only): DOC variants of the forward, dQ, dK/dV and
+// one-launch backward kernels, described before the forward kernel.
 #include <math.h>
 
 #include "common.h"
@@ -152,11 +154,22 @@ __device__ __forceinline__ void dma_barrier() {
   __syncthreads();
 }
 
-template <int D>
+// Document mask (DOC; causal only; packed sequences): kstart[b, i] = first key query i may see,
+// qend[b, j] = one past the last query that may see key j, both int32 [B, S] and non-decreasing
+// along S; query i sees key j iff kstart[i] <= j <= i, i.e. j <= i < qend[j]. The values are
+// clamped on load (kstart into [0, i], qend into [j + 1, S]) so that no contents can move a tile
+// range outside [0, S) or leave a query without its own key. DOC = false compiles to the code
+// without the mask: no extra register, no extra argument.
+__device__ __forceinline__ int clampi(int x, int lo, int hi) { return min(max(x, lo), hi); }
+__device__ __forceinline__ const int* doc_ptr(const int* p) { return p; }
+
+// Doc: empty (the plain kernel, whose signature it leaves as it was), or (const int* kstart)
+template <int D, typename... Doc>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
                                                        const __bf16* __restrict__ v, __bf16* __restrict__ o,
                                                        float* __restrict__ lse, int S, int Hq, int Hkv, float c,
-                                                       int causal) {
+                                                       int causal, Doc... doc) {
+  constexpr bool DOC = sizeof...(Doc) != 0;
   constexpr int KK = D / 16, DT = D / 32, TILE = kBN * D * 2;  // bytes of one K or V image
   extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 buffers][K image, V image]
   const int nqb = (S + kBM - 1) / kBM;
@@ -179,12 +192,23 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const __bf16* __restri
 
   const int kend = causal ? min(S, q0 + kBM) : S;
   const int nkt = (kend + kBN - 1) / kBN;
+  // DOC: this lane's kstart; the wave's first / last query's (wave-uniform; the arrays are monotone,
+  // so those are the wave's minimum / maximum); the block's first key tile (its first query's)
+  int ksi = 0, ksw = 0, ksh = 0, kt0 = 0;
+  if constexpr (DOC) {
+    const int* KS = doc_ptr(doc...) + (size_t)b * S;
+    const int qc = min(qi, S - 1);
+    ksi = clampi(KS[qc], 0, qc);
+    ksw = __builtin_amdgcn_readfirstlane(ksi);
+    ksh = __builtin_amdgcn_readlane(ksi, 31);
+    kt0 = clampi(KS[q0], 0, q0) / kBN;  // q0 < S; kt0 * kBN <= q0, so kt0 < nkt
+  }
   const Dma<D> dk(K, ks, S), dv(V, ks, S);
-  dk.issue(smem, 0);
-  dv.issue(smem + TILE, 0);
+  dk.issue(smem, kt0 * kBN);
+  dv.issue(smem + TILE, kt0 * kBN);
   dma_barrier();
-  for (int kt = 0; kt < nkt; ++kt) {
-    const int cur = kt & 1;
+  for (int kt = kt0; kt < nkt; ++kt) {
+    const int cur = DOC ? (kt - kt0) & 1 : kt & 1;  // buffer parity follows the loop's own count
     if (kt + 1 < nkt) {  // the other buffer: every wave finished reading it before the last barrier
       char* nx = smem + (cur ^ 1) * 2 * TILE;
       dk.issue(nx, (kt + 1) * kBN);
@@ -193,7 +217,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const __bf16* __restri
     const char* Kl = smem + cur * 2 * TILE;
     const char* Vl = Kl + TILE;
     const int k0 = kt * kBN;
-    if (!causal || k0 <= q0w + 31) {  // wave-uniform: some key of the tile is visible to this wave
+    // wave-uniform: some key of the tile is visible to this wave (DOC: and not wholly before the
+    // wave's first query's document)
+    if ((!causal || k0 <= q0w + 31) && (!DOC || k0 + kBN > ksw)) {
       f32x16 s[2];
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
@@ -201,7 +227,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const __bf16* __restri
 #pragma unroll
         for (int kk = 0; kk < KK; ++kk) s[t] = mfma(row_frag<D>(Kl, 32 * t + r, kk, h), qf[kk], s[t]);
       }
-      const bool edge = (causal && k0 + kBN - 1 > q0w) || k0 + kBN > S;
+      const bool edge = (causal && k0 + kBN - 1 > q0w) || k0 + kBN > S || (DOC && k0 < ksh);
       float mx = -INFINITY;
 #pragma unroll
       for (int t = 0; t < 2; ++t)
@@ -210,7 +236,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const __bf16* __restri
           float x = s[t][e] * c;
           if (edge) {
             const int key = k0 + 32 * t + acc_row(e, h);
-            if ((causal && key > qi) || key >= S) x = -INFINITY;
+            if ((causal && key > qi) || key >= S || (DOC && key < ksi)) x = -INFINITY;
           }
           s[t][e] = x;
           mx = fmaxf(mx, x);
@@ -280,12 +306,13 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const __bf16* __restric
   }
 }
 
-template <int D>
+template <int D, bool DOC>
 __device__ __forceinline__ void dq_body(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
                                                       const __bf16* __restrict__ v, const __bf16* __restrict__ dout,
                                                       const float* __restrict__ lse, const float* __restrict__ delta,
                                                       __bf16* __restrict__ dq, int S, int Hq, int Hkv, float c,
-                                                      float scale, int causal, int bx, int by, int bz) {
+                                                      float scale, int causal, int bx, int by, int bz,
+                                                      const int* __restrict__ kstart) {
   constexpr int KK = D / 16, DT = D / 32, TILE = kBN * D * 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int nqb = (S + kBM - 1) / kBM;
@@ -311,12 +338,21 @@ __device__ __forceinline__ void dq_body(const __bf16* __restrict__ q, const __bf
 
   const int kend = causal ? min(S, q0 + kBM) : S;
   const int nkt = (kend + kBN - 1) / kBN;
+  int ksi = 0, ksw = 0, ksh = 0, kt0 = 0;  // DOC: as in the forward
+  if constexpr (DOC) {
+    const int* KS = kstart + (size_t)b * S;
+    const int qc = min(qi, S - 1);
+    ksi = clampi(KS[qc], 0, qc);
+    ksw = __builtin_amdgcn_readfirstlane(ksi);
+    ksh = __builtin_amdgcn_readlane(ksi, 31);
+    kt0 = clampi(KS[q0], 0, q0) / kBN;
+  }
   const Dma<D> dmk(K, ks, S), dmv(V, ks, S);
-  dmk.issue(smem, 0);
-  dmv.issue(smem + TILE, 0);
+  dmk.issue(smem, kt0 * kBN);
+  dmv.issue(smem + TILE, kt0 * kBN);
   dma_barrier();
-  for (int kt = 0; kt < nkt; ++kt) {
-    const int cur = kt & 1;
+  for (int kt = kt0; kt < nkt; ++kt) {
+    const int cur = DOC ? (kt - kt0) & 1 : kt & 1;
     if (kt + 1 < nkt) {
       char* nx = smem + (cur ^ 1) * 2 * TILE;
       dmk.issue(nx, (kt + 1) * kBN);
@@ -330,19 +366,20 @@ __device__ __forceinline__ void dq_body(const __bf16* __restrict__ q, const __bf
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       if (causal && k0 + 32 * t > q0w + 31) continue;  // wave-uniform: the half is above the diagonal
+      if (DOC && k0 + 32 * t + 32 <= ksw) continue;     // ... or wholly before the wave's first document
       f32x16 s = zero16(), dp = zero16();
 #pragma unroll
       for (int kk = 0; kk < KK; ++kk) {
         s = mfma(row_frag<D>(Kl, 32 * t + r, kk, h), qf[kk], s);
         dp = mfma(row_frag<D>(Vl, 32 * t + r, kk, h), gf[kk], dp);
       }
-      const bool edge = (causal && k0 + 32 * t + 31 > q0w) || k0 + 32 * t + 32 > S;
+      const bool edge = (causal && k0 + 32 * t + 31 > q0w) || k0 + 32 * t + 32 > S || (DOC && k0 + 32 * t < ksh);
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         float p = __builtin_amdgcn_exp2f(s[e] * c - L2);
         if (edge) {
           const int key = k0 + 32 * t + acc_row(e, h);
-          if ((causal && key > qi) || key >= S) p = 0.f;
+          if ((causal && key > qi) || key >= S || (DOC && key < ksi)) p = 0.f;
         }
         s[e] = p * (dp[e] - dl);  // dS^T
       }
@@ -363,15 +400,26 @@ __global__ __launch_bounds__(256, 2) void attn_dq_kernel(const __bf16* __restric
                                                       const float* __restrict__ lse, const float* __restrict__ delta,
                                                       __bf16* __restrict__ dq, int S, int Hq, int Hkv, float c,
                                                       float scale, int causal) {
-  dq_body<D>(q, k, v, dout, lse, delta, dq, S, Hq, Hkv, c, scale, causal, blockIdx.x, blockIdx.y, blockIdx.z);
+  dq_body<D, false>(q, k, v, dout, lse, delta, dq, S, Hq, Hkv, c, scale, causal, blockIdx.x, blockIdx.y, blockIdx.z,
+                    nullptr);
 }
 
 template <int D>
+__global__ __launch_bounds__(256, 2) void attn_dq_doc_kernel(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
+                                                          const __bf16* __restrict__ v, const __bf16* __restrict__ dout,
+                                                          const float* __restrict__ lse, const float* __restrict__ delta,
+                                                          __bf16* __restrict__ dq, int S, int Hq, int Hkv, float c,
+                                                          float scale, const int* __restrict__ kstart) {
+  dq_body<D, true>(q, k, v, dout, lse, delta, dq, S, Hq, Hkv, c, scale, 1, blockIdx.x, blockIdx.y, blockIdx.z, kstart);
+}
+
+template <int D, bool DOC>
 __device__ __forceinline__ void dkdv_body(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
                                                         const __bf16* __restrict__ v, const __bf16* __restrict__ dout,
                                                         const float* __restrict__ lse, const float* __restrict__ delta,
                                                         __bf16* __restrict__ dk, __bf16* __restrict__ dv, int S, int Hq,
-                                                        int Hkv, float c, float scale, int causal, int bx, int by, int bz) {
+                                                        int Hkv, float c, float scale, int causal, int bx, int by, int bz,
+                                                        const int* __restrict__ qend) {
   constexpr int KK = D / 16, DT = D / 32, TILE = kBN * D * 2;
   // [2 buffers][Q image, dO image, L2[64], delta[64]]
   constexpr int BUF = 2 * TILE + 2 * kBN * 4;
@@ -397,7 +445,17 @@ __device__ __forceinline__ void dkdv_body(const __bf16* __restrict__ q, const __
   }
   // query tiles of 64: from the block's first key (causal) to the end, for every head of the group
   const int qt0 = causal ? (kb * kBM) / kBN : 0;
-  const int nqt = (S + kBN - 1) / kBN - qt0;
+  // DOC: this lane's qend; the wave's last key's (wave-uniform, the wave's maximum); the query range
+  // ends with the document of the block's last key
+  int qej = S, qew = S, qlim = S;
+  if constexpr (DOC) {
+    const int* QE = qend + (size_t)b * S;
+    const int kc = min(kj, S - 1), kl = min(kb * kBM + kBM - 1, S - 1);
+    qej = clampi(QE[kc], kc + 1, S);
+    qew = __builtin_amdgcn_readlane(qej, 31);
+    qlim = clampi(QE[kl], kl + 1, S);  // > kb * kBM: at least one query tile
+  }
+  const int nqt = (qlim + kBN - 1) / kBN - qt0;
   const int total = nqt * grp;
   // Q / dO tiles by LDS-DMA; L2 / delta (64 floats each) through registers
   auto store = [&](int it, int buf) {
@@ -431,6 +489,7 @@ __device__ __forceinline__ void dkdv_body(const __bf16* __restrict__ q, const __
       const int qu = q0 + 32 * u;  // this 32-query slice
       if (causal && qu + 31 < kw0) continue;  // wave-uniform: every query precedes this wave's keys
       if (qu >= S) continue;
+      if (DOC && qu >= qew) continue;  // wave-uniform: every query is past this wave's last document
       f32x16 s = zero16(), dp = zero16();
 #pragma unroll
       for (int kk = 0; kk < KK; ++kk) {
@@ -443,7 +502,7 @@ __device__ __forceinline__ void dkdv_body(const __bf16* __restrict__ q, const __
       for (int e = 0; e < 16; ++e) {
         const int qr = 32 * u + acc_row(e, h), qq = q0 + qr;
         float p = __builtin_amdgcn_exp2f(s[e] * c - L2s[qr]);
-        if ((causal && kj > qq) || qq >= S || kj >= S) p = 0.f;
+        if ((causal && kj > qq) || qq >= S || kj >= S || (DOC && qq >= qej)) p = 0.f;
         s[e] = p;
         ds[e] = p * (dp[e] - Dls[qr]);
       }
@@ -473,8 +532,21 @@ __global__ __launch_bounds__(256) void attn_dkdv_kernel(const __bf16* __restrict
   // first. At one wave per SIMD (356 VGPR+AGPR) the 512 blocks of the Llama-3-8B shape run in two
   // rounds on 256 CUs; heaviest-first keeps the second round from starting with a 16x-longer block.
   const int L = (int)blockIdx.x;
-  dkdv_body<D>(q, k, v, dout, lse, delta, dk, dv, S, Hq, Hkv, c, scale, causal, L / (Hkv * B), L % Hkv,
-               (L / Hkv) % B);
+  dkdv_body<D, false>(q, k, v, dout, lse, delta, dk, dv, S, Hq, Hkv, c, scale, causal, L / (Hkv * B), L % Hkv,
+                      (L / Hkv) % B, nullptr);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void attn_dkdv_doc_kernel(const __bf16* __restrict__ q, const __bf16* __restrict__ k,
+                                                            const __bf16* __restrict__ v,
+                                                            const __bf16* __restrict__ dout,
+                                                            const float* __restrict__ lse,
+                                                            const float* __restrict__ delta, __bf16* __restrict__ dk,
+                                                            __bf16* __restrict__ dv, int S, int Hq, int Hkv, int B,
+                                                            float c, float scale, const int* __restrict__ qend) {
+  const int L = (int)blockIdx.x;  // the same order as attn_dkdv_kernel
+  dkdv_body<D, true>(q, k, v, dout, lse, delta, dk, dv, S, Hq, Hkv, c, scale, 1, L / (Hkv * B), L % Hkv,
+                     (L / Hkv) % B, qend);
 }
 
 // Causal backward in ONE launch: the dK/dV blocks first (key block ascending = most query tiles
@@ -494,11 +566,34 @@ __global__ __launch_bounds__(256) void attn_bwd_fused_kernel(const __bf16* __res
   const int n_kv = nb * Hkv * B;
   int L = (int)blockIdx.x;
   if (L < n_kv) {  // key block slowest-varying: all heads' heaviest key blocks dispatch first
-    dkdv_body<D>(q, k, v, dout, lse, delta, dk, dv, S, Hq, Hkv, c, scale, causal, L / (Hkv * B), L % Hkv,
-                 (L / Hkv) % B);
+    dkdv_body<D, false>(q, k, v, dout, lse, delta, dk, dv, S, Hq, Hkv, c, scale, causal, L / (Hkv * B), L % Hkv,
+                        (L / Hkv) % B, nullptr);
   } else {
     L -= n_kv;
-    dq_body<D>(q, k, v, dout, lse, delta, dq, S, Hq, Hkv, c, scale, causal, L / (Hq * B), L % Hq, (L / Hq) % B);
+    dq_body<D, false>(q, k, v, dout, lse, delta, dq, S, Hq, Hkv, c, scale, causal, L / (Hq * B), L % Hq,
+                      (L / Hq) % B, nullptr);
+  }
+}
+
+// The document-masked backward in one launch: the same bodies in the same block order. With
+// documents of uneven length "key block ascending" is no longer "heaviest first" (a key block's
+// work ends with its document); the order is not re-balanced for that.
+template <int D>
+__global__ __launch_bounds__(256) void attn_bwd_fused_doc_kernel(
+    const __bf16* __restrict__ q, const __bf16* __restrict__ k, const __bf16* __restrict__ v,
+    const __bf16* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ delta,
+    __bf16* __restrict__ dq, __bf16* __restrict__ dk, __bf16* __restrict__ dv, int S, int Hq, int Hkv, int B, float c,
+    float scale, const int* __restrict__ kstart, const int* __restrict__ qend) {
+  const int nb = (S + kBM - 1) / kBM;
+  const int n_kv = nb * Hkv * B;
+  int L = (int)blockIdx.x;
+  if (L < n_kv) {
+    dkdv_body<D, true>(q, k, v, dout, lse, delta, dk, dv, S, Hq, Hkv, c, scale, 1, L / (Hkv * B), L % Hkv,
+                       (L / Hkv) % B, qend);
+  } else {
+    L -= n_kv;
+    dq_body<D, true>(q, k, v, dout, lse, delta, dq, S, Hq, Hkv, c, scale, 1, L / (Hq * B), L % Hq, (L / Hq) % B,
+                     kstart);
   }
 }
 
@@ -528,6 +623,16 @@ hipError_t launch_fwd(const void* q, const void* k, const void* v, void* o, floa
 }
 
 template <int D>
+hipError_t launch_fwd_doc(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int Hq,
+                          int Hkv, float scale, const int* kstart, hipStream_t st) {
+  const dim3 grid((S + kBM - 1) / kBM, Hq, B);
+  hipLaunchKernelGGL((attn_fwd_kernel<D, const int*>), grid, dim3(256), fwd_lds<D>(), st, (const __bf16*)q,
+                     (const __bf16*)k, (const __bf16*)v, (__bf16*)o, lse, S, Hq, Hkv, scale * 1.4426950408889634f, 1,
+                     kstart);
+  return hipGetLastError();
+}
+
+template <int D>
 hipError_t launch_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
                       float* delta, void* dq, void* dk, void* dv, int B, int S, int Hq, int Hkv, float scale, int causal,
                       hipStream_t st) {
@@ -552,6 +657,31 @@ hipError_t launch_bwd(const void* q, const void* k, const void* v, const void* o
   return hipGetLastError();
 }
 
+template <int D>
+hipError_t launch_bwd_doc(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                          const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int S, int Hq, int Hkv,
+                          float scale, const int* kstart, const int* qend, hipStream_t st) {
+  const int rows = B * S * Hq;
+  hipLaunchKernelGGL(attn_delta_kernel<D>, dim3((rows + 15) / 16), dim3(256), 0, st, (const __bf16*)o,
+                     (const __bf16*)dout, delta, B, S, Hq);
+  const float c = scale * 1.4426950408889634f;
+  const int nb = (S + kBM - 1) / kBM;
+  if (attn_bwd_fused()) {
+    const size_t lds = dkdv_lds<D>() > fwd_lds<D>() ? dkdv_lds<D>() : fwd_lds<D>();
+    hipLaunchKernelGGL(attn_bwd_fused_doc_kernel<D>, dim3(nb * (Hkv + Hq) * B), dim3(256), lds, st, (const __bf16*)q,
+                       (const __bf16*)k, (const __bf16*)v, (const __bf16*)dout, lse, delta, (__bf16*)dq, (__bf16*)dk,
+                       (__bf16*)dv, S, Hq, Hkv, B, c, scale, kstart, qend);
+    return hipGetLastError();
+  }
+  hipLaunchKernelGGL(attn_dq_doc_kernel<D>, dim3(nb, Hq, B), dim3(256), fwd_lds<D>(), st, (const __bf16*)q,
+                     (const __bf16*)k, (const __bf16*)v, (const __bf16*)dout, lse, delta, (__bf16*)dq, S, Hq, Hkv, c,
+                     scale, kstart);
+  hipLaunchKernelGGL(attn_dkdv_doc_kernel<D>, dim3(nb * Hkv * B), dim3(256), dkdv_lds<D>(), st, (const __bf16*)q,
+                     (const __bf16*)k, (const __bf16*)v, (const __bf16*)dout, lse, delta, (__bf16*)dk, (__bf16*)dv, S,
+                     Hq, Hkv, B, c, scale, qend);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t cs_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int Hq, int Hkv,
@@ -568,5 +698,26 @@ hipError_t cs_attn_bwd(const void* q, const void* k, const void* v, const void* 
   if (B == 0 || S == 0) return hipSuccess;
   if (D == 128) return launch_bwd<128>(q, k, v, o, dout, lse, delta, dq, dk, dv, B, S, Hq, Hkv, scale, causal, stream);
   if (D == 64) return launch_bwd<64>(q, k, v, o, dout, lse, delta, dq, dk, dv, B, S, Hq, Hkv, scale, causal, stream);
+  return hipErrorInvalidValue;
+}
+
+hipError_t cs_attn_fwd_doc(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int Hq,
+                           int Hkv, int D, float scale, const int* kstart, hipStream_t stream) {
+  if (B == 0 || S == 0) return hipSuccess;
+  if (kstart == nullptr) return hipErrorInvalidValue;
+  if (D == 128) return launch_fwd_doc<128>(q, k, v, o, lse, B, S, Hq, Hkv, scale, kstart, stream);
+  if (D == 64) return launch_fwd_doc<64>(q, k, v, o, lse, B, S, Hq, Hkv, scale, kstart, stream);
+  return hipErrorInvalidValue;
+}
+
+hipError_t cs_attn_bwd_doc(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                           const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int S, int Hq, int Hkv,
+                           int D, float scale, const int* kstart, const int* qend, hipStream_t stream) {
+  if (B == 0 || S == 0) return hipSuccess;
+  if (kstart == nullptr || qend == nullptr) return hipErrorInvalidValue;
+  if (D == 128)
+    return launch_bwd_doc<128>(q, k, v, o, dout, lse, delta, dq, dk, dv, B, S, Hq, Hkv, scale, kstart, qend, stream);
+  if (D == 64)
+    return launch_bwd_doc<64>(q, k, v, o, dout, lse, delta, dq, dk, dv, B, S, Hq, Hkv, scale, kstart, qend, stream);
   return hipErrorInvalidValue;
 }

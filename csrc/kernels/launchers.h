@@ -375,6 +375,15 @@ hipError_t cs_attn_fwd(const void* q, const void* k, const void* v, void* o, flo
 hipError_t cs_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
                        float* delta, void* dq, void* dk, void* dv, int B, int S, int Hq, int Hkv, int D, float scale,
                        int causal, hipStream_t stream);
+// the same, causal with a document mask (packed sequences): kstart / qend int32 [B, S], non-decreasing
+// along S; query i sees key j iff kstart[b, i] <= j <= i, i.e. j <= i < qend[b, j]. Values are clamped
+// in the kernels (kstart into [0, i], qend into [j + 1, S]): no contents can cause an access outside
+// the tensors. The forward and the dQ pass read kstart, the dK/dV pass reads qend.
+hipError_t cs_attn_fwd_doc(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int Hq,
+                           int Hkv, int D, float scale, const int* kstart, hipStream_t stream);
+hipError_t cs_attn_bwd_doc(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                           const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int S, int Hq, int Hkv,
+                           int D, float scale, const int* kstart, const int* qend, hipStream_t stream);
 // training BatchNorm2d (+ residual add, + ReLU) on NCHW fp32 / bf16 activations (bn_nchw.hip).
 // stat: f32 [4, C] = scale, shift, mean, invstd (written by the forward, read by the backward);
 // part: f32 scratch of cs_bn_nchw_partials(N, C) floats; coef: f32 [3, C] scratch (backward).
