@@ -36,21 +36,28 @@ def rope_ref(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Ten
 
 
 # ------------------------------------------------------------------ autograd functions
+def _aligned(t: torch.Tensor) -> torch.Tensor:
+    """``t`` contiguous and 16-byte aligned, as the RMSNorm 4-wide and the cross-entropy kernels read
+    it (8 / 16-byte vector accesses; the bindings refuse anything else): a contiguous view at an odd
+    storage offset is copied into a fresh allocation, everything else is returned as it is."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 class _RMSNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, eps, out_bf16):
-        xc = x.contiguous()
-        y, rstd = native.C().rmsnorm_fwd(xc, w.contiguous(), eps, out_bf16)
+        xc = _aligned(x)
+        y, rstd = native.C().rmsnorm_fwd(xc, _aligned(w), eps, out_bf16)
         ctx.save_for_backward(xc, w, rstd)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, w, rstd = ctx.saved_tensors
-        gy = gy.contiguous()
-        if gy.dtype != x.dtype and x.shape[-1] % 4 != 0:
-            gy = gy.to(x.dtype)
-        dx, dw = native.C().rmsnorm_bwd(x, w.contiguous(), rstd, gy)
+        if gy.dtype != x.dtype and not native.C().rmsnorm_vec4(x.shape[-1]):
+            gy = gy.to(x.dtype)  # the scalar kernels read the gradient in x's dtype
+        dx, dw = native.C().rmsnorm_bwd(x, _aligned(w), rstd, _aligned(gy))
         return dx, dw, None, None
 
 
@@ -91,7 +98,7 @@ def rms_norm(x: torch.Tensor, w: torch.Tensor, eps: float = 1e-5) -> torch.Tenso
         # projections that follow read it without a cast pass each (5 per block), and their input
         # gradients come back in bf16 into the backward kernel, again without a cast
         out_bf16 = (torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16
-                    and x.shape[-1] % 4 == 0)
+                    and native.C().rmsnorm_vec4(x.shape[-1]))  # the scalar kernels (D % 4, D > 8192) keep x's dtype
         return _RMSNorm.apply(x, w, eps, out_bf16)
     return rms_norm_ref(x, w, eps)
 
@@ -224,6 +231,7 @@ class ShadowLinear(torch.nn.Linear):
 class _CrossEntropy(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, targets):
+        logits = _aligned(logits)
         loss, lse = native.C().xent_fwd(logits, targets)
         ctx.save_for_backward(logits, targets, lse)
         return loss.sum() / logits.shape[0]

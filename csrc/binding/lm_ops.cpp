@@ -1,4 +1,7 @@
 // torch bindings of the decoder-LM kernels (csrc/kernels/lm.hip); shapes/dtypes validated on the host.
+#include <climits>
+#include <cstdint>
+
 #include "binding/torch_util.h"
 #include "kernels/launchers.h"
 
@@ -18,16 +21,26 @@ void check(const torch::Tensor& t, const char* n) {
   TORCH_CHECK(t.is_cuda() && t.is_contiguous(), n, " must be a contiguous GPU tensor");
 }
 
+// operands of the 16-byte (fp32 x4) / 8-byte (bf16 x4) vector accesses of the RMSNorm 4-wide and the
+// cross-entropy kernels: a contiguous view at an odd storage offset passes check() but not this
+// (ops/lm.py re-materialises such a view before the call)
+void check_aligned(const torch::Tensor& t, const char* n) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, n, " must be 16-byte aligned");
+}
+
 // out_bf16: write y in bf16 whatever x's dtype (the fp32 residual stream feeding bf16 GEMMs)
 std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w, double eps, bool out_bf16) {
   check(x, "x"); check(w, "w");
   const int64_t D = w.numel();
   TORCH_CHECK(x.size(-1) == D, "rmsnorm: last dim must match the weight");
-  TORCH_CHECK(!out_bf16 || x.scalar_type() == at::kBFloat16 || D % 4 == 0, "rmsnorm: bf16 output of fp32 input needs D % 4 == 0");
+  const bool vec4 = cs_rmsnorm_vec4((int)D);
+  TORCH_CHECK(!out_bf16 || x.scalar_type() == at::kBFloat16 || vec4,
+              "rmsnorm: bf16 output of fp32 input needs D % 4 == 0 and D <= 8192");
   const int64_t rows = x.numel() / D;
   DevGuard g(x.device());
   auto y = out_bf16 ? torch::empty_like(x, x.options().dtype(at::kBFloat16)) : torch::empty_like(x);
   auto rstd = torch::empty({rows}, x.options().dtype(at::kFloat));
+  if (vec4) { check_aligned(x, "x"); check_aligned(w, "w"); check_aligned(y, "y"); }
   CS_LAUNCH(cs_rmsnorm_fwd(dt_of(x), dt_of(w), dt_of(y), x.data_ptr(), w.data_ptr(), y.data_ptr(),
                            rstd.data_ptr<float>(), (int)rows, (int)D, (float)eps, cur_stream()));
   return {y, rstd};
@@ -37,11 +50,16 @@ std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor x, torch::Tensor w, torch::
   check(x, "x"); check(w, "w"); check(rstd, "rstd"); check(gy, "gy");
   const int64_t D = w.numel(), rows = x.numel() / D;
   TORCH_CHECK(gy.sizes() == x.sizes() && rstd.numel() == rows, "rmsnorm_bwd: shapes");
-  TORCH_CHECK(gy.scalar_type() == x.scalar_type() || D % 4 == 0, "rmsnorm_bwd: mixed dtypes need D % 4 == 0");
+  const bool vec4 = cs_rmsnorm_vec4((int)D);
+  TORCH_CHECK(gy.scalar_type() == x.scalar_type() || vec4, "rmsnorm_bwd: mixed dtypes need D % 4 == 0 and D <= 8192");
   DevGuard g(x.device());
   auto dx = torch::empty_like(x);
   auto dw = torch::empty_like(w);
   auto part = torch::empty({(int64_t)cs_rmsnorm_bwd_partials((int)rows, (int)D), D}, x.options().dtype(at::kFloat));
+  if (vec4) {
+    check_aligned(x, "x"); check_aligned(w, "w"); check_aligned(gy, "gy");
+    check_aligned(dx, "dx"); check_aligned(dw, "dw"); check_aligned(part, "part");
+  }
   CS_LAUNCH(cs_rmsnorm_bwd(dt_of(x), dt_of(w), dt_of(gy), x.data_ptr(), w.data_ptr(), rstd.data_ptr<float>(),
                            gy.data_ptr(), dx.data_ptr(), dw.data_ptr(), part.data_ptr<float>(), (int)rows, (int)D,
                            cur_stream()));
@@ -57,6 +75,7 @@ std::vector<torch::Tensor> xent_fwd(torch::Tensor logits, torch::Tensor tgt) {
   DevGuard g(logits.device());
   auto fo = logits.options().dtype(at::kFloat);
   auto loss = torch::empty({logits.size(0)}, fo), lse = torch::empty({logits.size(0)}, fo);
+  check_aligned(logits, "logits");
   CS_LAUNCH(cs_xent_fwd(dt_of(logits), logits.data_ptr(), tgt.data_ptr<int64_t>(), loss.data_ptr<float>(),
                         lse.data_ptr<float>(), (int)logits.size(0), (int)logits.size(1), cur_stream()));
   return {loss, lse};
@@ -70,6 +89,7 @@ torch::Tensor xent_bwd(torch::Tensor logits, torch::Tensor tgt, torch::Tensor ls
   TORCH_CHECK(gscale.is_cuda() && gscale.scalar_type() == at::kFloat && gscale.numel() == 1, "xent_bwd: g");
   DevGuard g(logits.device());
   auto d = torch::empty_like(logits);
+  check_aligned(logits, "logits"); check_aligned(d, "dlogits");
   CS_LAUNCH(cs_xent_bwd(dt_of(logits), logits.data_ptr(), tgt.data_ptr<int64_t>(), lse.data_ptr<float>(),
                         gscale.data_ptr<float>(), (float)inv_n, d.data_ptr(), (int)logits.size(0), (int)logits.size(1),
                         cur_stream()));
@@ -268,6 +288,8 @@ std::vector<torch::Tensor> mm_bf16_bn_stats(torch::Tensor a, torch::Tensor b) {
 }  // namespace
 
 void register_lm_ops(pybind11::module& m) {
+  m.def("rmsnorm_vec4", [](int64_t D) { return D > 0 && D <= INT_MAX && cs_rmsnorm_vec4((int)D); },
+        "whether RMSNorm of width D runs the 4-wide kernels (aligned operands; mixed dtypes allowed)");
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
   m.def("rmsnorm_bwd", &rmsnorm_bwd);
   m.def("xent_fwd", &xent_fwd, "softmax cross-entropy rows -> (loss, lse)");

@@ -352,7 +352,10 @@ hipError_t cs_clock_stop(int* stop, hipStream_t stream);
 // ---------------------------------------------------------------- decoder-LM elementwise ops (lm.hip)
 enum { CS_F32 = 0, CS_BF16 = 1 };
 int cs_rmsnorm_bwd_partials(int rows, int D);
-// y has dtype odt (e.g. bf16 out of an fp32 residual stream under autocast; odt != dt needs D % 4 == 0)
+// whether RMSNorm of width D runs the 4-wide kernels (D % 4 == 0 and D <= 8192): their 16-byte (fp32) /
+// 8-byte (bf16) accesses need x, w, y, g, dx and dw 16-byte aligned, and only they mix dtypes
+bool cs_rmsnorm_vec4(int D);
+// y has dtype odt (e.g. bf16 out of an fp32 residual stream under autocast; odt != dt needs cs_rmsnorm_vec4(D))
 hipError_t cs_rmsnorm_fwd(int dt, int wdt, int odt, const void* x, const void* w, void* y, float* rstd, int rows,
                           int D, float eps, hipStream_t s);
 // part: [cs_rmsnorm_bwd_partials(rows, D)][D] fp32 scratch; dw has the weight's dtype, g dtype gdt, dx x's

@@ -223,15 +223,25 @@ __global__ __launch_bounds__(256) void swiglu_fwd_kernel(const T* __restrict__ a
   }
 }
 
+// One definition for the scalar and the 4-wide backward, with the one fusable multiply-add written as
+// an fma: left to -ffp-contract the compiler fused it in the 4-wide kernels and in the scalar loop's
+// steady state but not in its peeled first trip, so the same element could differ by an ulp between
+// the two kernels (and with its position in the grid).
+__device__ __forceinline__ void swiglu_grad1(float a, float b, float g, float& da, float& db) {
+  const float s = sigmoidf(a);
+  da = g * b * s * fmaf(a, 1.f - s, 1.f);
+  db = g * a * s;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const T* __restrict__ a, const T* __restrict__ b,
                                                          const T* __restrict__ g, T* __restrict__ da,
                                                          T* __restrict__ db, size_t n) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float av = ld(a, i), bv = ld(b, i), gv = ld(g, i);
-    const float s = sigmoidf(av);
-    st(da, i, gv * bv * s * (1.f + av * (1.f - s)));
-    st(db, i, gv * av * s);
+    float x, y;
+    swiglu_grad1(ld(a, i), ld(b, i), ld(g, i), x, y);
+    st(da, i, x);
+    st(db, i, y);
   }
 }
 
@@ -245,12 +255,6 @@ __global__ __launch_bounds__(256) void swiglu_fwd4_kernel(const T* __restrict__ 
     st4(out + 4 * i, make_float4(av.x * sigmoidf(av.x) * bv.x, av.y * sigmoidf(av.y) * bv.y,
                                  av.z * sigmoidf(av.z) * bv.z, av.w * sigmoidf(av.w) * bv.w));
   }
-}
-
-__device__ __forceinline__ void swiglu_grad1(float a, float b, float g, float& da, float& db) {
-  const float s = sigmoidf(a);
-  da = g * b * s * (1.f + a * (1.f - s));
-  db = g * a * s;
 }
 
 template <typename T>
@@ -387,6 +391,8 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(const T* __restrict__ log
 bool use4(int D) { return D % 4 == 0 && D / 4 <= 256 * kMaxQ; }
 
 }  // namespace
+
+bool cs_rmsnorm_vec4(int D) { return use4(D); }
 
 int cs_rmsnorm_bwd_partials(int rows, int D) {
   return use4(D) ? (rows + kRows4 - 1) / kRows4 : (rows + kRowsPerBlock - 1) / kRowsPerBlock;
