@@ -243,12 +243,115 @@ class _CrossEntropy(torch.autograd.Function):
         return d, None
 
 
-def cross_entropy(logits: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
+# no ignore index: the kernels compare every target with a value no token id takes
+_NO_IGNORE = -(1 << 63)
+
+
+class _CrossEntropyMasked(torch.autograd.Function):
+    """The masked / z-regularised kernels. The sum, the valid-row count, its reciprocal and the mean
+    are formed on the device (``stats``); the backward reads the reciprocal there: no host read-back."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, ignore, z):
+        logits = _aligned(logits)
+        _, lse, stats = native.C().xent_fwd_masked(logits, targets, ignore, z)
+        ctx.save_for_backward(logits, targets, lse, stats)
+        ctx.ignore, ctx.z = ignore, z
+        return stats[3].float()
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, targets, lse, stats = ctx.saved_tensors
+        d = native.C().xent_bwd_masked(logits, targets, lse, stats, g.float().reshape(1).contiguous(), ctx.ignore,
+                                       ctx.z)
+        return d, None, None, None
+
+
+def _xent_native_ok(logits: torch.Tensor) -> bool:
+    return (logits.is_cuda and logits.dim() == 2 and logits.shape[1] % 8 == 0
+            and logits.dtype in (torch.float32, torch.bfloat16))
+
+
+def _xent_rows_ref(logits, targets, ignore_index, z_loss):
+    """fp32 per-row losses (0 for an ignored row, NaN for any other target outside [0, V)) and the
+    mask of the rows that count. An ignored row's logits are replaced before any arithmetic, as the
+    kernels never read them: a NaN there reaches neither the loss nor the gradient."""
+    x = logits.float()
+    V = x.shape[-1]
+    valid = torch.ones_like(targets, dtype=torch.bool) if ignore_index is None else targets != ignore_index
+    x = torch.where(valid[:, None], x, torch.zeros((), dtype=x.dtype, device=x.device))
+    lse = torch.logsumexp(x, -1)
+    inside = (targets >= 0) & (targets < V)
+    xt = x.gather(1, targets.clamp(0, V - 1)[:, None])[:, 0]
+    rows = lse - torch.where(inside, xt, torch.full_like(xt, float("nan")))
+    if z_loss != 0.0:
+        rows = rows + z_loss * lse * lse
+    return torch.where(valid, rows, torch.zeros_like(rows)), valid
+
+
+def cross_entropy_ref(logits: torch.Tensor, targets: torch.Tensor, ignore_index=None,
+                      z_loss: float = 0.0) -> torch.Tensor:
+    """Plain-torch ``cross_entropy`` with the semantics of the masked kernels, in fp32: the mean over
+    the rows whose target is not ``ignore_index`` of ``(lse - x_t) + z_loss * lse^2``; 0 (and a zero
+    gradient) when every row is ignored; NaN when a non-ignored target lies outside [0, V), with the
+    gradient of the softmax term alone for that row."""
+    rows, valid = _xent_rows_ref(logits, targets, ignore_index, z_loss)
+    inv = (1.0 / valid.sum().clamp(min=1).double()).float()  # a double division rounded once, on the device
+    return rows.sum() * inv
+
+
+def cross_entropy(logits: torch.Tensor, targets: torch.Tensor, ignore_index=None,
+                  z_loss: float = 0.0) -> torch.Tensor:
     """``F.cross_entropy(logits.float(), targets)`` (mean over rows) for [R, V] logits: on GPU one
     fused gfx950 pass forward and one backward over the logits in their own dtype (no fp32 upcast of
-    the [tokens, vocab] matrix, no separate log-softmax / nll / cast kernels). Targets must lie in
-    [0, V) (no ignore index; the LM's synthetic tokens always do)."""
-    if (logits.is_cuda and logits.dim() == 2 and logits.shape[1] % 8 == 0
-            and logits.dtype in (torch.float32, torch.bfloat16)):
-        return _CrossEntropy.apply(logits.contiguous(), targets.contiguous())
-    return torch.nn.functional.cross_entropy(logits.float(), targets)
+    the [tokens, vocab] matrix, no separate log-softmax / nll / cast kernels).
+
+    ``ignore_index`` (default ``None``: no ignore index, not torch's -100): rows with that target,
+    negative or inside the vocabulary (a pad id), are left out of the loss and get a zero gradient;
+    the forward kernel does not read their logits. The mean runs over the remaining rows. Unlike
+    ``F.cross_entropy``, a batch in which every row is ignored gives loss 0 and an all-zero gradient,
+    not 0 / 0 = NaN: an all-padding micro-batch must not poison the weights.
+    ``z_loss`` (>= 0) adds ``z_loss * lse^2`` per row, the auxiliary loss that keeps the softmax
+    normaliser near 1 (PaLM, OLMo 2); its gradient is one multiply per element in the same backward pass.
+    Every other target must lie in [0, V): one outside makes the loss NaN.
+
+    With ``ignore_index=None`` and ``z_loss == 0`` the launches are those of the unmasked kernels,
+    unchanged. Otherwise GPU fp32 / bf16 logits with V % 8 == 0 run the masked kernels, anything else
+    (CPU, another V or dtype) ``cross_entropy_ref`` with the same semantics.
+
+    Data-parallel runs: every rank's mean is over its own valid rows, and the gradient all-reduce then
+    averages the ranks with equal weight (the usual convention, not a global valid-token mean)."""
+    z_loss = float(z_loss)
+    if ignore_index is None and z_loss == 0.0:
+        if _xent_native_ok(logits):
+            return _CrossEntropy.apply(logits.contiguous(), targets.contiguous())
+        return torch.nn.functional.cross_entropy(logits.float(), targets)
+    if not (z_loss >= 0.0 and z_loss != float("inf")):
+        raise ValueError(f"z_loss must be finite and >= 0, got {z_loss}")
+    if _xent_native_ok(logits) and targets.is_cuda and targets.dtype == torch.int64:
+        ignore = _NO_IGNORE if ignore_index is None else int(ignore_index)
+        return _CrossEntropyMasked.apply(logits.contiguous(), targets.contiguous(), ignore, z_loss)
+    return cross_entropy_ref(logits, targets, ignore_index, z_loss)
+
+
+@torch.no_grad()
+def cross_entropy_sums(logits: torch.Tensor, targets: torch.Tensor, ignore_index=None):
+    """Forward only, no z-loss: ``(nll_sum, n_valid)`` as 0-dim device tensors (float64, int64), the
+    sum of ``lse - x_t`` over the rows whose target is not ``ignore_index`` and their number. On GPU
+    these are the device statistics of the masked forward; nothing is read back. Token-weighted
+    evaluation accumulates them over batches and divides once."""
+    if _xent_native_ok(logits) and targets.is_cuda and targets.dtype == torch.int64:
+        ignore = _NO_IGNORE if ignore_index is None else int(ignore_index)
+        stats = native.C().xent_fwd_masked(_aligned(logits), targets.contiguous(), ignore, 0.0)[2]
+        return stats[0], stats[1].long()
+    rows, valid = _xent_rows_ref(logits, targets, ignore_index, 0.0)
+    return rows.double().sum(), valid.sum()
+
+
+def mask_boundary_targets(inputs: torch.Tensor, targets: torch.Tensor, eos_id: int,
+                          ignore_index: int = -100) -> torch.Tensor:
+    """The targets of a packed batch with every position whose *input* is ``eos_id`` set to
+    ``ignore_index`` (one device op, nothing read back). Convention of ``ops.attention.doc_ids_from_eos``:
+    an EOS closes its own document, so the target at an EOS input is the first token of the next
+    document, which document-masked attention has made unpredictable."""
+    return targets.masked_fill(inputs == eos_id, ignore_index)

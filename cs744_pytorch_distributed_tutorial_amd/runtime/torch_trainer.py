@@ -19,12 +19,16 @@ framework's own data-parallel runtime around them.
   (``dtype="bf16"``; master weights and the optimizer stay fp32);
 * data = device-resident synthetic batches of the named shape (no host traffic); for the LM,
   ``doc_len=N`` / ``CS744_DOC_LEN=N`` packs documents of about N tokens into every row and trains
-  with document-masked attention (``ops.attention``), the mask derived from the EOS tokens each step.
+  with document-masked attention (``ops.attention``), the mask derived from the EOS tokens each step;
+  ``loss_mask="doc"`` / ``CS744_LOSS_MASK=doc`` then drops the targets that cross a document boundary
+  from the loss, ``z_loss=z`` / ``CS744_Z_LOSS=z`` adds the z-loss (``ops.lm.cross_entropy``), and
+  ``evaluate()`` reports the z-free, token-weighted negative log-likelihood and perplexity.
 """
 from __future__ import annotations
 
 from typing import Optional
 
+import math
 import os
 
 import torch
@@ -98,11 +102,21 @@ class TorchTrainer:
                  comm: str = "rccl", bucket_mb: float = 25.0, bucket_policy: str = "layer", dtype: str = "fp32",
                  lr: float = 0.1, momentum: float = 0.9, weight_decay: float = 1e-4, seed: int = 5000,
                  seq_len: int = 0, fused_sgd: bool = True, optimizer: Optional[str] = None, betas=(0.9, 0.95),
-                 eps: float = 1e-8, max_grad_norm: Optional[float] = None, doc_len: Optional[int] = None):
+                 eps: float = 1e-8, max_grad_norm: Optional[float] = None, doc_len: Optional[int] = None,
+                 loss_mask: Optional[str] = None, z_loss: Optional[float] = None):
         """``doc_len``: pack documents of about that many tokens into every row of the synthetic token
         pool (``SyntheticBatches``) and train with document-masked attention: ``step()`` derives the
         document of every token from the EOS tokens of its input, the way real packed data would be
         handled. ``None`` takes ``CS744_DOC_LEN`` if set, else no document masking. LM models only.
+
+        ``loss_mask="doc"`` (needs ``doc_len``): the target at every EOS input, the first token of the next
+        document, which the document mask has made unpredictable, is set to the ignore index -100
+        (``ops.lm.mask_boundary_targets``) and takes no loss and no gradient. ``z_loss``: the coefficient
+        of the auxiliary ``z * lse^2`` per token. ``None`` takes ``CS744_LOSS_MASK`` / ``CS744_Z_LOSS`` if
+        set, else no mask / no z-loss. LM models only. The loss is the mean over the rank's own valid
+        tokens; with several ranks the gradient all-reduce then averages the ranks with equal weight
+        (the usual convention; not a global valid-token mean). ``tokens_per_step()`` still counts every
+        token processed.
 
         ``optimizer``: ``"sgd"`` (momentum SGD, the default) or ``"adamw"`` (AdamW with decoupled weight
         decay on the parameters with ``dim() >= 2`` only, and global-norm gradient clipping at
@@ -176,6 +190,19 @@ class TorchTrainer:
         if doc_len is not None and not self.is_lm:
             raise ValueError(f"doc_len (document-masked attention) is for the LM models, not {model!r}")
         self.doc_len = doc_len
+        if loss_mask is None and "CS744_LOSS_MASK" in os.environ:
+            loss_mask = os.environ["CS744_LOSS_MASK"].lower()
+        if z_loss is None and "CS744_Z_LOSS" in os.environ:
+            z_loss = float(os.environ["CS744_Z_LOSS"])
+        if (loss_mask is not None or z_loss is not None) and not self.is_lm:
+            raise ValueError(f"loss_mask / z_loss are for the LM models, not {model!r}")
+        if loss_mask not in (None, "doc"):
+            raise ValueError(f"unknown loss_mask {loss_mask!r} ('doc' or None)")
+        if loss_mask == "doc" and doc_len is None:
+            raise ValueError("loss_mask='doc' needs doc_len (the documents whose boundaries it masks)")
+        if z_loss is not None and not (0.0 <= z_loss < math.inf):
+            raise ValueError(f"z_loss must be finite and >= 0, got {z_loss}")
+        self.loss_mask, self.z_loss = loss_mask, 0.0 if z_loss is None else float(z_loss)
         if self.is_lm:
             self.eos_id = self.module.cfg.eos_id
             self.data = SyntheticBatches("tokens", batch_size, device, seq=seq_len or self.module.max_seq,
@@ -201,7 +228,8 @@ class TorchTrainer:
                 out = self.net(x)
             if self.is_lm:  # fused gfx950 softmax cross-entropy over the bf16 logits (ops.lm)
                 from ..ops.lm import cross_entropy
-                loss = cross_entropy(out.view(-1, out.shape[-1]), y.view(-1))
+                loss = cross_entropy(out.view(-1, out.shape[-1]), self._targets(x, y).view(-1),
+                                     ignore_index=self._ignore_index(), z_loss=self.z_loss)
             else:
                 loss = self.crit(out.float(), y)
         with roctx_range("cs.backward"):  # DDP's bucket all-reduces are enqueued from its hooks in here
@@ -214,6 +242,49 @@ class TorchTrainer:
                                                self.clip_norm)
             self.opt.step()
         self.loss = loss.detach()
+
+    def _ignore_index(self) -> Optional[int]:
+        return -100 if self.loss_mask == "doc" else None
+
+    def _targets(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        if self.loss_mask == "doc":
+            from ..ops.lm import mask_boundary_targets
+            return mask_boundary_targets(x, y, self.eos_id, -100)
+        return y
+
+    def evaluate(self, batches: int) -> dict:
+        """Forward only over ``batches`` fresh batches of the same pool, in eval mode under ``no_grad``,
+        with the trainer's document mask and loss mask: ``{"nll", "ppl", "tokens"}``, the negative
+        log-likelihood summed over the valid tokens of all batches divided by their number, its
+        exponential, and that number. No z-loss in it: this is the token-weighted figure that the
+        training loss no longer is once ``z_loss > 0``. The sums stay on the device and are read back
+        once. With several ranks every rank reports its own batches' numbers. LM models only."""
+        if not self.is_lm:
+            raise ValueError("evaluate() is for the LM models")
+        from ..ops.lm import cross_entropy_sums
+        was_training = self.net.training
+        self.net.eval()
+        acc = torch.zeros(2, dtype=torch.float64, device=self.device)  # (nll sum, valid tokens): exact counts to 2^53
+        try:
+            with torch.no_grad():
+                for _ in range(batches):
+                    x, y = self.data.next()
+                    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.dtype == "bf16"):
+                        if self.doc_len is not None:
+                            from ..ops.attention import doc_ids_from_eos
+                            out = self.net(x, doc_ids=doc_ids_from_eos(x, self.eos_id))
+                        else:
+                            out = self.net(x)
+                        s, n = cross_entropy_sums(out.view(-1, out.shape[-1]), self._targets(x, y).view(-1),
+                                                  ignore_index=self._ignore_index())
+                    acc[0] += s
+                    acc[1] += n
+        finally:
+            self.net.train(was_training)
+        total, tokens = acc.tolist()  # the one read-back
+        tokens = int(tokens)
+        mean = total / max(tokens, 1)
+        return {"nll": mean, "ppl": math.exp(mean) if mean < 700 else math.inf, "tokens": tokens}
 
     def last_loss(self) -> float:
         return float(self.loss.item()) if self.loss is not None else float("nan")

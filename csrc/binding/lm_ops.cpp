@@ -1,5 +1,7 @@
 // torch bindings of the decoder-LM kernels (csrc/kernels/lm.hip); shapes/dtypes validated on the host.
+#include <cfloat>
 #include <climits>
+#include <cmath>
 #include <cstdint>
 
 #include "binding/torch_util.h"
@@ -93,6 +95,58 @@ torch::Tensor xent_bwd(torch::Tensor logits, torch::Tensor tgt, torch::Tensor ls
   CS_LAUNCH(cs_xent_bwd(dt_of(logits), logits.data_ptr(), tgt.data_ptr<int64_t>(), lse.data_ptr<float>(),
                         gscale.data_ptr<float>(), (float)inv_n, d.data_ptr(), (int)logits.size(0), (int)logits.size(1),
                         cur_stream()));
+  return d;
+}
+
+// the host checks shared by the masked pair, all before any launch
+void xent_masked_check(const torch::Tensor& logits, const torch::Tensor& tgt, double z_loss, const char* fn) {
+  check(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(1) > 0 && logits.size(1) % 8 == 0, fn,
+              ": logits [R, V] with V % 8 == 0");
+  TORCH_CHECK(logits.size(0) <= INT_MAX && logits.size(1) <= INT_MAX, fn, ": dimension too large");
+  TORCH_CHECK(tgt.is_cuda() && tgt.device() == logits.device() && tgt.is_contiguous() &&
+                  tgt.scalar_type() == at::kLong && tgt.numel() == logits.size(0),
+              fn, ": targets [R] int64, contiguous, on the logits' device");
+  TORCH_CHECK(std::isfinite(z_loss) && z_loss >= 0.0 && z_loss <= FLT_MAX, fn,
+              ": z_loss must be a finite float >= 0, got ", z_loss);
+  check_aligned(logits, "logits");
+}
+
+void xent_stats_check(const torch::Tensor& stats, const torch::Tensor& logits, const char* fn) {
+  TORCH_CHECK(stats.is_cuda() && stats.device() == logits.device(), fn, ": stats must be on the logits' device");
+  TORCH_CHECK(stats.scalar_type() == at::kDouble, fn, ": stats must be float64, got ", stats.scalar_type());
+  TORCH_CHECK(stats.dim() == 1 && stats.numel() == 4 && stats.is_contiguous(), fn, ": stats must be a contiguous [4]");
+}
+
+// logits [R, V], targets [R] int64 -> {loss_rows [R] f32, lse [R] f32, stats [4] f64 = (sum, n_valid, inv, mean)}
+std::vector<torch::Tensor> xent_fwd_masked(torch::Tensor logits, torch::Tensor tgt, int64_t ignore_index,
+                                           double z_loss) {
+  xent_masked_check(logits, tgt, z_loss, "xent_fwd_masked");
+  DevGuard g(logits.device());
+  auto fo = logits.options().dtype(at::kFloat);
+  auto loss = torch::empty({logits.size(0)}, fo), lse = torch::empty({logits.size(0)}, fo);
+  auto stats = torch::empty({4}, logits.options().dtype(at::kDouble));
+  CS_LAUNCH(cs_xent_fwd_masked(dt_of(logits), logits.data_ptr(), tgt.data_ptr<int64_t>(), loss.data_ptr<float>(),
+                               lse.data_ptr<float>(), stats.data_ptr<double>(), (int)logits.size(0),
+                               (int)logits.size(1), ignore_index, (float)z_loss, cur_stream()));
+  return {loss, lse, stats};
+}
+
+torch::Tensor xent_bwd_masked(torch::Tensor logits, torch::Tensor tgt, torch::Tensor lse, torch::Tensor stats,
+                              torch::Tensor gscale, int64_t ignore_index, double z_loss) {
+  xent_masked_check(logits, tgt, z_loss, "xent_bwd_masked");
+  TORCH_CHECK(lse.is_cuda() && lse.device() == logits.device() && lse.is_contiguous() &&
+                  lse.scalar_type() == at::kFloat && lse.numel() == logits.size(0),
+              "xent_bwd_masked: lse [R] float32");
+  xent_stats_check(stats, logits, "xent_bwd_masked");
+  TORCH_CHECK(gscale.is_cuda() && gscale.device() == logits.device() && gscale.scalar_type() == at::kFloat &&
+                  gscale.numel() == 1, "xent_bwd_masked: g must be one float32 element on the logits' device");
+  DevGuard g(logits.device());
+  auto d = torch::empty_like(logits);
+  check_aligned(d, "dlogits");
+  CS_LAUNCH(cs_xent_bwd_masked(dt_of(logits), logits.data_ptr(), tgt.data_ptr<int64_t>(), lse.data_ptr<float>(),
+                               gscale.data_ptr<float>(), stats.data_ptr<double>(), d.data_ptr(), (int)logits.size(0),
+                               (int)logits.size(1), ignore_index, (float)z_loss, cur_stream()));
   return d;
 }
 
@@ -294,6 +348,10 @@ void register_lm_ops(pybind11::module& m) {
   m.def("rmsnorm_bwd", &rmsnorm_bwd);
   m.def("xent_fwd", &xent_fwd, "softmax cross-entropy rows -> (loss, lse)");
   m.def("xent_bwd", &xent_bwd, "its backward -> dlogits");
+  m.def("xent_fwd_masked", &xent_fwd_masked,
+        "softmax cross-entropy rows with an ignore index and a z-loss -> (loss, lse, stats = [sum, n_valid, inv, "
+        "mean])");
+  m.def("xent_bwd_masked", &xent_bwd_masked, "its backward -> dlogits (scaled by g * stats[2], read on the device)");
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("rope", &rope);

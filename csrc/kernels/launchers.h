@@ -367,6 +367,16 @@ hipError_t cs_xent_fwd(int dt, const void* logits, const int64_t* tgt, float* lo
                        hipStream_t s);
 hipError_t cs_xent_bwd(int dt, const void* logits, const int64_t* tgt, const float* lse, const float* g, float inv_n,
                        void* dlogits, int R, int V, hipStream_t s);
+// the same with an ignore index and a z-loss: rows whose target == ignore are skipped (loss = lse = 0, a
+// zero dlogits row, their logits never read), every other row's loss is (lse - x_t) + z * lse^2, and the
+// mean runs over the non-ignored rows. The forward also writes stats (4 doubles, on the device, in a
+// fixed order): {sum of the row losses, n_valid, inv = (float)(1.0 / max(n_valid, 1)), mean = sum * inv};
+// the backward reads inv from there: dlogits = (softmax * (1 + 2 z lse) - onehot) * g[0] * inv.
+hipError_t cs_xent_fwd_masked(int dt, const void* logits, const int64_t* tgt, float* loss, float* lse, double* stats,
+                              int R, int V, int64_t ignore, float z, hipStream_t s);
+hipError_t cs_xent_bwd_masked(int dt, const void* logits, const int64_t* tgt, const float* lse, const float* g,
+                              const double* stats, void* dlogits, int R, int V, int64_t ignore, float z,
+                              hipStream_t s);
 hipError_t cs_swiglu_fwd(int dt, const void* a, const void* b, void* out, size_t n, hipStream_t s);
 hipError_t cs_swiglu_bwd(int dt, const void* a, const void* b, const void* g, void* da, void* db, size_t n,
                          hipStream_t s);

@@ -327,12 +327,9 @@ __device__ __forceinline__ void ld8(const T* p, float (&v)[8]) {
   v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
 }
 
+// log-sum-exp of one row of V logits by the block's 256 threads: valid in thread 0 only
 template <typename T>
-__global__ __launch_bounds__(256) void xent_fwd_kernel(const T* __restrict__ logits, const int64_t* __restrict__ tgt,
-                                                       float* __restrict__ loss, float* __restrict__ lse, int V) {
-  __shared__ float sm[4], ss[4];
-  const int row = blockIdx.x;
-  const T* x = logits + (size_t)row * V;
+__device__ __forceinline__ float xent_row_lse(const T* __restrict__ x, int V, float* sm, float* ss) {
   float m = -INFINITY, s = 0.f;
   for (int i = threadIdx.x * 8; i < V; i += 256 * 8) {
     float v[8];
@@ -355,11 +352,21 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(const T* __restrict__ log
     ss[threadIdx.x >> 6] = s;
   }
   __syncthreads();
-  if (threadIdx.x != 0) return;
+  if (threadIdx.x != 0) return 0.f;
   m = sm[0];
   s = ss[0];
   for (int w = 1; w < 4; ++w) ms_combine(m, s, sm[w], ss[w]);
-  const float l = m + __logf(s);
+  return m + __logf(s);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void xent_fwd_kernel(const T* __restrict__ logits, const int64_t* __restrict__ tgt,
+                                                       float* __restrict__ loss, float* __restrict__ lse, int V) {
+  __shared__ float sm[4], ss[4];
+  const int row = blockIdx.x;
+  const T* x = logits + (size_t)row * V;
+  const float l = xent_row_lse(x, V, sm, ss);
+  if (threadIdx.x != 0) return;
   lse[row] = l;
   const int64_t t = tgt[row];
   loss[row] = (t >= 0 && t < V) ? l - ld(x, (size_t)t) : NAN;  // an out-of-range target poisons the loss
@@ -381,6 +388,129 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(const T* __restrict__ log
     float o[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) o[j] = (__expf(v[j] - l) - (i + j == t ? 1.f : 0.f)) * scale;
+    a = make_float4(o[0], o[1], o[2], o[3]);
+    b = make_float4(o[4], o[5], o[6], o[7]);
+    st4(d + i, a);
+    st4(d + i + 4, b);
+  }
+}
+
+// ---- the same with an ignore index and a z-loss (z * lse^2 per row), mean over the rows whose
+// target is not the ignore index. A row with the ignore index costs the forward nothing (the block
+// leaves before it loads a logit; loss = lse = 0) and the backward one write of zeros. Any other
+// target outside [0, V) poisons the loss as above. stats (double[4], written by xent_reduce_kernel):
+// {sum of the row losses, n_valid, inv = (float)(1.0 / max(n_valid, 1)), mean = (float)(sum * inv)}
+template <typename T>
+__global__ __launch_bounds__(256) void xent_fwd_masked_kernel(const T* __restrict__ logits,
+                                                              const int64_t* __restrict__ tgt,
+                                                              float* __restrict__ loss, float* __restrict__ lse,
+                                                              int V, int64_t ignore, float z) {
+  __shared__ float sm[4], ss[4];
+  const int row = blockIdx.x;
+  const int64_t t = tgt[row];
+  if (t == ignore) {  // uniform across the block: safe ahead of the barrier in xent_row_lse
+    if (threadIdx.x == 0) {
+      loss[row] = 0.f;
+      lse[row] = 0.f;
+    }
+    return;
+  }
+  const T* x = logits + (size_t)row * V;
+  const float l = xent_row_lse(x, V, sm, ss);
+  if (threadIdx.x != 0) return;
+  lse[row] = l;
+  if (t < 0 || t >= V) {
+    loss[row] = NAN;
+    return;
+  }
+  const float nll = l - ld(x, (size_t)t);
+  loss[row] = z != 0.f ? nll + z * l * l : nll;  // z == 0: the bits of xent_fwd_kernel, also for an infinite lse
+}
+
+// one block of 1024 threads: thread i sums rows i, i + 1024, ... in ascending order in double, then a
+// fixed tree over the threads; no atomics, the same bits every run. Eight rows per trip with the
+// loads issued together at clamped (in-bounds) indices: the kernel is a chain of memory latencies,
+// not of bandwidth. Rows with an out-of-range target count as valid (their NaN poisons the sum anyway).
+constexpr int kRedThreads = 1024, kRedBatch = 8;
+
+__global__ __launch_bounds__(kRedThreads) void xent_reduce_kernel(const float* __restrict__ loss,
+                                                                  const int64_t* __restrict__ tgt, int R,
+                                                                  int64_t ignore, double* __restrict__ stats) {
+#pragma clang fp contract(off)
+  __shared__ double rs[kRedThreads];
+  __shared__ int rn[kRedThreads];
+  double acc = 0.0;
+  int n = 0;
+  for (int64_t base = threadIdx.x; base < R; base += kRedThreads * kRedBatch) {
+    float v[kRedBatch];
+    int64_t t[kRedBatch];
+#pragma unroll
+    for (int k = 0; k < kRedBatch; ++k) {
+      const int64_t i = base + (int64_t)k * kRedThreads, j = i < R ? i : R - 1;
+      v[k] = loss[j];
+      t[k] = i < R ? tgt[j] : ignore;
+    }
+#pragma unroll
+    for (int k = 0; k < kRedBatch; ++k) {
+      if (t[k] != ignore) {
+        acc += (double)v[k];
+        ++n;
+      }
+    }
+  }
+  rs[threadIdx.x] = acc;
+  rn[threadIdx.x] = n;
+  __syncthreads();
+#pragma unroll
+  for (int s = kRedThreads / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      rs[threadIdx.x] += rs[threadIdx.x + s];
+      rn[threadIdx.x] += rn[threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  const int nv = rn[0];
+  const float inv = (float)(1.0 / (double)(nv > 1 ? nv : 1));  // a double division rounded once, as Python's 1.0 / R
+  stats[0] = rs[0];
+  stats[1] = (double)nv;
+  stats[2] = (double)inv;
+  stats[3] = (double)(float)(rs[0] * (double)inv);  // no valid row: 0 * 1 = 0, not 0 / 0
+}
+
+// ZL = false: the arithmetic of xent_bwd_kernel with inv_n = stats[2] (no multiply by 1)
+template <typename T, bool ZL>
+__global__ __launch_bounds__(256) void xent_bwd_masked_kernel(const T* __restrict__ logits,
+                                                              const int64_t* __restrict__ tgt,
+                                                              const float* __restrict__ lse,
+                                                              const float* __restrict__ g,
+                                                              const double* __restrict__ stats,
+                                                              T* __restrict__ dlogits, int V, int64_t ignore,
+                                                              float z) {
+  const int row = blockIdx.x;
+  T* d = dlogits + (size_t)row * V;
+  const int64_t t = tgt[row];
+  if (t == ignore) {  // dlogits is uninitialised memory: the row is written, its logits are not read
+    // 16 bytes per lane whatever T: a write-only block gets nothing else to hide half-filled stores behind
+    uint4* dz = reinterpret_cast<uint4*>(d);
+    const int nvec = V / (16 / (int)sizeof(T));  // V % 8 == 0 and a 16-byte aligned base: whole vectors
+    for (int i = threadIdx.x; i < nvec; i += 256) dz[i] = make_uint4(0u, 0u, 0u, 0u);
+    return;
+  }
+  const T* x = logits + (size_t)row * V;
+  const float l = lse[row], scale = g[0] * (float)stats[2];
+  const float c = 1.f + 2.f * z * l;  // d(lse + z lse^2) / d lse
+  for (int i = threadIdx.x * 8; i < V; i += 256 * 8) {
+    float v[8];
+    ld8(x + i, v);
+    float4 a, b;
+    float o[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float p = __expf(v[j] - l);
+      if (ZL) p *= c;
+      o[j] = (p - (i + j == t ? 1.f : 0.f)) * scale;
+    }
     a = make_float4(o[0], o[1], o[2], o[3]);
     b = make_float4(o[4], o[5], o[6], o[7]);
     st4(d + i, a);
@@ -486,6 +616,31 @@ hipError_t cs_xent_bwd(int dt, const void* logits, const int64_t* tgt, const flo
   if (V % 8 != 0) return hipErrorInvalidValue;
   CS_DT_DISPATCH(dt, hipLaunchKernelGGL((xent_bwd_kernel<T>), dim3(R), dim3(256), 0, s, (const T*)logits, tgt, lse, g,
                                         inv_n, (T*)dlogits, V));
+  return hipGetLastError();
+}
+
+hipError_t cs_xent_fwd_masked(int dt, const void* logits, const int64_t* tgt, float* loss, float* lse, double* stats,
+                              int R, int V, int64_t ignore, float z, hipStream_t s) {
+  if (R < 0 || V <= 0 || V % 8 != 0 || !(z >= 0.f) || stats == nullptr) return hipErrorInvalidValue;
+  if (R > 0)
+    CS_DT_DISPATCH(dt, hipLaunchKernelGGL((xent_fwd_masked_kernel<T>), dim3(R), dim3(256), 0, s, (const T*)logits, tgt,
+                                          loss, lse, V, ignore, z));
+  hipLaunchKernelGGL(xent_reduce_kernel, dim3(1), dim3(kRedThreads), 0, s, loss, tgt, R, ignore, stats);
+  return hipGetLastError();
+}
+
+hipError_t cs_xent_bwd_masked(int dt, const void* logits, const int64_t* tgt, const float* lse, const float* g,
+                              const double* stats, void* dlogits, int R, int V, int64_t ignore, float z,
+                              hipStream_t s) {
+  if (R <= 0) return hipSuccess;
+  if (V % 8 != 0 || !(z >= 0.f) || stats == nullptr) return hipErrorInvalidValue;
+  if (z != 0.f) {
+    CS_DT_DISPATCH(dt, hipLaunchKernelGGL((xent_bwd_masked_kernel<T, true>), dim3(R), dim3(256), 0, s,
+                                          (const T*)logits, tgt, lse, g, stats, (T*)dlogits, V, ignore, z));
+  } else {
+    CS_DT_DISPATCH(dt, hipLaunchKernelGGL((xent_bwd_masked_kernel<T, false>), dim3(R), dim3(256), 0, s,
+                                          (const T*)logits, tgt, lse, g, stats, (T*)dlogits, V, ignore, z));
+  }
   return hipGetLastError();
 }
 
