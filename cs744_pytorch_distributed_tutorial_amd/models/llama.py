@@ -154,11 +154,23 @@ class Llama(nn.Module):
             self._rope = rope_tables(max(S, 1), self.cfg.dim // self.cfg.n_heads, self.cfg.rope_theta, device)
         return self._rope[0][:S], self._rope[1][:S]
 
-    def forward(self, tokens: torch.Tensor, doc_ids: torch.Tensor = None) -> torch.Tensor:
+    def forward(self, tokens: torch.Tensor, doc_ids: torch.Tensor = None, targets: torch.Tensor = None,
+                ignore_index=None, z_loss: float = 0.0) -> torch.Tensor:
         """``doc_ids``: integer [B, S], the document of every token of a packed batch
         (``ops.attention.doc_ids_from_eos``); attention is then confined to a token's own document.
         RoPE positions are NOT reset per document: a RoPE score depends only on ``i - j``, so inside
-        a document the result is the same as with positions counted from the document's start."""
+        a document the result is the same as with positions counted from the document's start.
+
+        Without ``targets`` the logits [B, S, V] are returned. With ``targets`` (int64 [B, S]) the
+        result is the loss ``ops.lm.cross_entropy(logits, targets, ignore_index, z_loss)`` computed by
+        ``ops.lm.linear_cross_entropy`` over row chunks: the logits are never built whole."""
+        h = self.hidden(tokens, doc_ids)
+        if targets is None:
+            return self.output(h)
+        return _ops().linear_cross_entropy(h, self.output, targets, ignore_index=ignore_index, z_loss=z_loss)
+
+    def hidden(self, tokens: torch.Tensor, doc_ids: torch.Tensor = None) -> torch.Tensor:
+        """The final-norm hidden states [B, S, D] that the output head reads."""
         S = tokens.shape[1]
         cos, sin = self._tables(S, tokens.device)
         h = self.tok_embeddings(tokens)
@@ -170,7 +182,7 @@ class Llama(nn.Module):
             doc = doc_bounds(doc_ids)  # once per forward, shared by every layer
             for blk in self.layers:
                 h = blk(h, cos, sin, doc)
-        return self.output(self.norm(h))
+        return self.norm(h)
 
 
 def build(name: str) -> Llama:

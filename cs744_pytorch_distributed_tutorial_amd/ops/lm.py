@@ -348,6 +348,189 @@ def cross_entropy_sums(logits: torch.Tensor, targets: torch.Tensor, ignore_index
     return rows.double().sum(), valid.sum()
 
 
+# ------------------------------------------------------------------ chunked LM head: linear + loss
+def head_chunk_rows(R: int, V: int, itemsize: int, chunk_rows=None) -> int:
+    """Rows of one logits chunk of the fused head. An explicit ``chunk_rows`` is clamped to [1, R];
+    otherwise the rows of a chunk of ``CS_LM_HEAD_CHUNK_MB`` MiB (default 1024) of logits, rounded down
+    to a multiple of 256 (the GEMM's tile), at least 256 and at most R."""
+    R = max(int(R), 1)
+    if chunk_rows is not None:
+        return min(max(int(chunk_rows), 1), R)
+    mb = float(os.environ.get("CS_LM_HEAD_CHUNK_MB", "1024"))
+    if not mb > 0:
+        raise ValueError(f"CS_LM_HEAD_CHUNK_MB must be > 0, got {mb}")
+    rows = int(mb * (1 << 20)) // (int(V) * int(itemsize))
+    return min(max(rows // 256 * 256, 256), R)
+
+
+def linear_cross_entropy_ref(h: torch.Tensor, head: torch.nn.Linear, targets: torch.Tensor, ignore_index=None,
+                             z_loss: float = 0.0) -> torch.Tensor:
+    """The unfused head: the full logits, then ``cross_entropy`` over them."""
+    logits = head(h)
+    return cross_entropy(logits.view(-1, logits.shape[-1]), targets.reshape(-1), ignore_index, z_loss)
+
+
+def _head_mode(h: torch.Tensor, head, targets: torch.Tensor):
+    """"bf16" / "fp32": how the chunked loop runs its GEMMs; None: the reference path"""
+    w = getattr(head, "weight", None)
+    if not isinstance(head, torch.nn.Linear) or head.bias is not None or not (h.is_cuda and w.is_cuda and
+                                                                                targets.is_cuda):
+        return None
+    if w.dtype != torch.float32 or targets.dtype != torch.int64 or w.shape[0] % 8 or h.numel() == 0:
+        return None
+    if h.shape[-1] != w.shape[1] or targets.numel() != h.numel() // h.shape[-1]:
+        return None
+    if torch.is_autocast_enabled("cuda"):
+        if (torch.get_autocast_dtype("cuda") == torch.bfloat16 and isinstance(head, ShadowLinear)
+                and h.dtype in (torch.float32, torch.bfloat16)):
+            return "bf16"
+        return None
+    return "fp32" if h.dtype == torch.float32 else None
+
+
+def _mm_into(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out = a @ b, ``out`` a contiguous row block of the result's dtype: the GEMM that ``_mm`` picks
+    (CS_LM_GEMM=native: the GEMM makes its own output, which is copied into ``out``)"""
+    if _GEMM == "native" and a.dtype == torch.bfloat16 and gemm_operands_ok(a, b):
+        return out.copy_(native.C().mm_bf16(a, b))
+    return torch.mm(a, b, out=out)
+
+
+def _head_logits(hc, wmat, buf):
+    """hc @ wmat^T for one chunk, in the one reused buffer (CS_LM_GEMM=native: the GEMM's own output,
+    freed before the next chunk's is made, so that no copy of the chunk is needed)"""
+    if _GEMM == "native" and wmat.dtype == torch.bfloat16 and gemm_operands_ok(hc, wmat.t()):
+        return native.C().mm_bf16(hc, wmat.t())
+    if buf[0] is None:
+        buf[0] = torch.empty(buf[1], wmat.shape[0], dtype=hc.dtype, device=hc.device)
+    return torch.mm(hc, wmat.t(), out=buf[0][:hc.shape[0]])
+
+
+class _LinearCrossEntropy(torch.autograd.Function):
+    """The head GEMM, the loss and both gradients over row chunks; only one chunk of logits exists at a
+    time. ``xent_fused_`` turns the chunk into its gradient in place (scaled by 1 / n_valid, counted over
+    all rows before the first chunk), the chunk then feeds dh_c = dlogits_c W and dW += dlogits_c^T h_c
+    (fp32). The gradients are finished in forward; backward multiplies them by the upstream scalar."""
+
+    @staticmethod
+    def forward(ctx, h2, weight, shadow, targets, ignore, z, chunk):
+        C = native.C()
+        wmat = weight.detach() if shadow is None else shadow
+        R, D = h2.shape
+        V = wmat.shape[0]
+        need_h, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        bf16 = wmat.dtype == torch.bfloat16
+        with torch.autocast("cuda", enabled=False):
+            loss = torch.empty(R, dtype=torch.float32, device=h2.device)
+            if need_h or need_w:
+                stats = C.xent_count(targets, ignore)  # 1 / n_valid over all rows, before the first chunk
+                lse = torch.empty_like(loss)
+            else:
+                stats = torch.empty(4, dtype=torch.float64, device=h2.device)
+            buf = [None, min(chunk, R)]
+            dh = torch.empty_like(h2) if need_h else None
+            dW = torch.zeros(V, D, dtype=torch.float32, device=h2.device) if need_w else None
+            for r0 in range(0, R, chunk):
+                hc = h2[r0:r0 + chunk]
+                lc = _head_logits(hc, wmat, buf)
+                if not (need_h or need_w):  # forward only: the loss rows of this chunk, nothing else
+                    loss[r0:r0 + chunk] = C.xent_fwd_masked(lc, targets[r0:r0 + chunk], ignore, z)[0]
+                    del lc
+                    continue
+                C.xent_fused_(lc, targets, loss, lse, stats, r0, ignore, z)
+                if need_h:
+                    _mm_into(lc, wmat, dh[r0:r0 + chunk])
+                if need_w:
+                    if not bf16:
+                        dW.addmm_(lc.t(), hc)
+                    elif _GEMM != "blas" and gemm_operands_ok(lc.t(), hc):
+                        C.mm_bf16(lc.t(), hc, True, dW, 1)  # fp32 +=, no reduction split: K is one chunk
+                    else:
+                        dW += torch.mm(lc.t(), hc, out_dtype=torch.float32)
+                del lc
+            C.xent_reduce(loss, targets, ignore, stats)
+        # plain attributes on purpose, not save_for_backward: they are neither inputs nor outputs, backward
+        # scales them in place and hands them out, and a second backward (retain_graph) is refused below
+        ctx.dh, ctx.dW = dh, dW
+        return stats[3].float()
+
+    @staticmethod
+    def backward(ctx, g):
+        dh, dW = ctx.dh, ctx.dW
+        ctx.dh = ctx.dW = None  # scaled in place: a second backward through this node has nothing to return
+        if dh is None and dW is None and any(ctx.needs_input_grad[:2]):
+            raise RuntimeError("linear_cross_entropy: backward ran twice; its gradients are scaled in place")
+        g = g.float()
+        if dh is not None:
+            dh.mul_(g)
+        if dW is not None:
+            dW.mul_(g)
+        return dh, dW, None, None, None, None, None
+
+
+def _head_args(h, head, targets, mode):
+    h2 = h.reshape(-1, h.shape[-1])
+    if mode == "bf16":
+        h2 = h2.to(torch.bfloat16)
+    return _aligned(h2), head._shadow() if mode == "bf16" else None, targets.reshape(-1).contiguous()
+
+
+def linear_cross_entropy(h: torch.Tensor, head: torch.nn.Linear, targets: torch.Tensor, ignore_index=None,
+                         z_loss: float = 0.0, chunk_rows=None) -> torch.Tensor:
+    """``cross_entropy(head(h).view(-1, V), targets.view(-1), ignore_index, z_loss)`` without the
+    [tokens, vocab] logits: the head GEMM, the fused loss kernel and the two gradient GEMMs run over
+    chunks of ``head_chunk_rows`` rows, so one chunk of logits (and no saved copy, no separate
+    gradient matrix) is alive at a time: in one reused buffer with the library GEMM (CS_LM_GEMM=wgrad,
+    the default, or blas), in a fresh allocation per chunk with CS_LM_GEMM=native. ``h``: [..., D]; ``head``: a bias-free ``nn.Linear``;
+    ``targets``: int64, one per row of ``h``. Returns the 0-dim fp32 loss; same masking, z-loss,
+    all-rows-ignored -> 0 and out-of-range -> NaN rules as ``cross_entropy``, and the same per-rank
+    mean under data parallelism.
+
+    On the GPU, under bf16 autocast with a ``ShadowLinear`` the GEMMs read the bf16 shadow and the fp32
+    weight gradient is accumulated by the native GEMM's ``+=`` mode; fp32 ``h`` without autocast runs the
+    same loop on ``torch.mm``. The gradients of ``h`` and of the weight are complete when forward
+    returns (backward only scales them by the upstream gradient, in place), which is what removes the
+    saved logits; under ``no_grad`` only the loss is computed. Anything else (CPU, V % 8 != 0, a bias,
+    other dtypes) runs ``linear_cross_entropy_ref``."""
+    z_loss = float(z_loss)
+    if not (z_loss >= 0.0 and z_loss != float("inf")):
+        raise ValueError(f"z_loss must be finite and >= 0, got {z_loss}")
+    mode = _head_mode(h, head, targets)
+    if mode is None:
+        return linear_cross_entropy_ref(h, head, targets, ignore_index, z_loss)
+    h2, shadow, t = _head_args(h, head, targets, mode)
+    chunk = head_chunk_rows(h2.shape[0], head.weight.shape[0], h2.element_size(), chunk_rows)
+    ignore = _NO_IGNORE if ignore_index is None else int(ignore_index)
+    return _LinearCrossEntropy.apply(h2, head.weight, shadow, t, ignore, z_loss, chunk)
+
+
+@torch.no_grad()
+def linear_cross_entropy_sums(h: torch.Tensor, head: torch.nn.Linear, targets: torch.Tensor, ignore_index=None,
+                              chunk_rows=None):
+    """``cross_entropy_sums(head(h).view(-1, V), targets.view(-1), ignore_index)``, forward only and
+    chunked like ``linear_cross_entropy``: ``(nll_sum, n_valid)`` as 0-dim device tensors."""
+    mode = _head_mode(h, head, targets)
+    if mode is None:
+        logits = head(h)
+        return cross_entropy_sums(logits.view(-1, logits.shape[-1]), targets.reshape(-1), ignore_index)
+    C = native.C()
+    h2, shadow, t = _head_args(h, head, targets, mode)
+    wmat = head.weight.detach() if shadow is None else shadow
+    R, V = h2.shape[0], wmat.shape[0]
+    chunk = head_chunk_rows(R, V, h2.element_size(), chunk_rows)
+    ignore = _NO_IGNORE if ignore_index is None else int(ignore_index)
+    with torch.autocast("cuda", enabled=False):
+        loss = torch.empty(R, dtype=torch.float32, device=h2.device)
+        buf = [None, min(chunk, R)]
+        for r0 in range(0, R, chunk):
+            lc = _head_logits(h2[r0:r0 + chunk], wmat, buf)
+            loss[r0:r0 + chunk] = C.xent_fwd_masked(lc, t[r0:r0 + chunk], ignore, 0.0)[0]
+            del lc
+        stats = torch.empty(4, dtype=torch.float64, device=h2.device)
+        C.xent_reduce(loss, t, ignore, stats)
+    return stats[0], stats[1].long()
+
+
 def mask_boundary_targets(inputs: torch.Tensor, targets: torch.Tensor, eos_id: int,
                           ignore_index: int = -100) -> torch.Tensor:
     """The targets of a packed batch with every position whose *input* is ``eos_id`` set to

@@ -103,7 +103,7 @@ class TorchTrainer:
                  lr: float = 0.1, momentum: float = 0.9, weight_decay: float = 1e-4, seed: int = 5000,
                  seq_len: int = 0, fused_sgd: bool = True, optimizer: Optional[str] = None, betas=(0.9, 0.95),
                  eps: float = 1e-8, max_grad_norm: Optional[float] = None, doc_len: Optional[int] = None,
-                 loss_mask: Optional[str] = None, z_loss: Optional[float] = None):
+                 loss_mask: Optional[str] = None, z_loss: Optional[float] = None, fused_head: Optional[bool] = None):
         """``doc_len``: pack documents of about that many tokens into every row of the synthetic token
         pool (``SyntheticBatches``) and train with document-masked attention: ``step()`` derives the
         document of every token from the EOS tokens of its input, the way real packed data would be
@@ -117,6 +117,12 @@ class TorchTrainer:
         tokens; with several ranks the gradient all-reduce then averages the ranks with equal weight
         (the usual convention; not a global valid-token mean). ``tokens_per_step()`` still counts every
         token processed.
+
+        ``fused_head``: run the output projection and the loss together over row chunks
+        (``ops.lm.linear_cross_entropy``), so that the [tokens, vocab] logits and their gradient are never
+        built whole; ``step()`` hands targets, ignore index and z-loss to the model and ``evaluate()``
+        uses ``ops.lm.linear_cross_entropy_sums``. ``None`` takes ``CS744_FUSED_HEAD=1`` if set, else off.
+        LM models only. ``CS_LM_HEAD_CHUNK_MB`` sets the chunk size.
 
         ``optimizer``: ``"sgd"`` (momentum SGD, the default) or ``"adamw"`` (AdamW with decoupled weight
         decay on the parameters with ``dim() >= 2`` only, and global-norm gradient clipping at
@@ -203,6 +209,11 @@ class TorchTrainer:
         if z_loss is not None and not (0.0 <= z_loss < math.inf):
             raise ValueError(f"z_loss must be finite and >= 0, got {z_loss}")
         self.loss_mask, self.z_loss = loss_mask, 0.0 if z_loss is None else float(z_loss)
+        if fused_head is None:
+            fused_head = os.environ.get("CS744_FUSED_HEAD", "0") == "1"
+        if fused_head and not self.is_lm:
+            raise ValueError(f"fused_head (the chunked linear + cross-entropy head) is for the LM models, not {model!r}")
+        self.fused_head = bool(fused_head)
         if self.is_lm:
             self.eos_id = self.module.cfg.eos_id
             self.data = SyntheticBatches("tokens", batch_size, device, seq=seq_len or self.module.max_seq,
@@ -221,17 +232,21 @@ class TorchTrainer:
         x, y = self.data.next()
         self.opt.zero_grad()  # DDP re-attaches its bucket views (and zeroes them) in forward
         with roctx_range("cs.forward"), torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.dtype == "bf16"):
+            doc_ids = None
             if self.doc_len is not None:  # packed rows: documents end at the EOS tokens of the input
                 from ..ops.attention import doc_ids_from_eos
-                out = self.net(x, doc_ids=doc_ids_from_eos(x, self.eos_id))
+                doc_ids = doc_ids_from_eos(x, self.eos_id)
+            if self.fused_head:  # the model ends in the chunked head + loss: no [tokens, vocab] logits
+                loss = self.net(x, doc_ids=doc_ids, targets=self._targets(x, y), ignore_index=self._ignore_index(),
+                                z_loss=self.z_loss)
             else:
-                out = self.net(x)
-            if self.is_lm:  # fused gfx950 softmax cross-entropy over the bf16 logits (ops.lm)
-                from ..ops.lm import cross_entropy
-                loss = cross_entropy(out.view(-1, out.shape[-1]), self._targets(x, y).view(-1),
-                                     ignore_index=self._ignore_index(), z_loss=self.z_loss)
-            else:
-                loss = self.crit(out.float(), y)
+                out = self.net(x, doc_ids=doc_ids) if doc_ids is not None else self.net(x)
+                if self.is_lm:  # fused gfx950 softmax cross-entropy over the bf16 logits (ops.lm)
+                    from ..ops.lm import cross_entropy
+                    loss = cross_entropy(out.view(-1, out.shape[-1]), self._targets(x, y).view(-1),
+                                         ignore_index=self._ignore_index(), z_loss=self.z_loss)
+                else:
+                    loss = self.crit(out.float(), y)
         with roctx_range("cs.backward"):  # DDP's bucket all-reduces are enqueued from its hooks in here
             loss.backward()
         with roctx_range("cs.sync"):
@@ -261,7 +276,7 @@ class TorchTrainer:
         once. With several ranks every rank reports its own batches' numbers. LM models only."""
         if not self.is_lm:
             raise ValueError("evaluate() is for the LM models")
-        from ..ops.lm import cross_entropy_sums
+        from ..ops.lm import cross_entropy_sums, linear_cross_entropy_sums
         was_training = self.net.training
         self.net.eval()
         acc = torch.zeros(2, dtype=torch.float64, device=self.device)  # (nll sum, valid tokens): exact counts to 2^53
@@ -270,13 +285,17 @@ class TorchTrainer:
                 for _ in range(batches):
                     x, y = self.data.next()
                     with torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.dtype == "bf16"):
+                        doc_ids = None
                         if self.doc_len is not None:
                             from ..ops.attention import doc_ids_from_eos
-                            out = self.net(x, doc_ids=doc_ids_from_eos(x, self.eos_id))
+                            doc_ids = doc_ids_from_eos(x, self.eos_id)
+                        if self.fused_head:  # the head and the sums over row chunks (no DDP hooks under no_grad)
+                            s, n = linear_cross_entropy_sums(self.module.hidden(x, doc_ids), self.module.output,
+                                                             self._targets(x, y), ignore_index=self._ignore_index())
                         else:
-                            out = self.net(x)
-                        s, n = cross_entropy_sums(out.view(-1, out.shape[-1]), self._targets(x, y).view(-1),
-                                                  ignore_index=self._ignore_index())
+                            out = self.net(x, doc_ids=doc_ids) if doc_ids is not None else self.net(x)
+                            s, n = cross_entropy_sums(out.view(-1, out.shape[-1]), self._targets(x, y).view(-1),
+                                                      ignore_index=self._ignore_index())
                     acc[0] += s
                     acc[1] += n
         finally:

@@ -150,6 +150,61 @@ torch::Tensor xent_bwd_masked(torch::Tensor logits, torch::Tensor tgt, torch::Te
   return d;
 }
 
+// ---- the chunked LM head (ops/lm.py linear_cross_entropy)
+void xent_targets_check(const torch::Tensor& tgt, const char* fn) {
+  TORCH_CHECK(tgt.is_cuda() && tgt.is_contiguous() && tgt.scalar_type() == at::kLong && tgt.dim() == 1 &&
+                  tgt.numel() <= INT_MAX, fn, ": targets [R] int64, contiguous, on the GPU");
+}
+
+// targets [R] int64 -> stats [4] f64 = (0, n_valid, inv, 0), the count and reciprocal of xent_fwd_masked
+torch::Tensor xent_count(torch::Tensor tgt, int64_t ignore_index) {
+  xent_targets_check(tgt, "xent_count");
+  DevGuard g(tgt.device());
+  auto stats = torch::empty({4}, tgt.options().dtype(at::kDouble));
+  CS_LAUNCH(cs_xent_count(tgt.data_ptr<int64_t>(), (int)tgt.numel(), ignore_index, stats.data_ptr<double>(),
+                          cur_stream()));
+  return stats;
+}
+
+// the final statistics over the full loss vector: stats = (sum, n_valid, inv, mean), in place
+void xent_reduce(torch::Tensor loss, torch::Tensor tgt, int64_t ignore_index, torch::Tensor stats) {
+  xent_targets_check(tgt, "xent_reduce");
+  TORCH_CHECK(loss.is_cuda() && loss.device() == tgt.device() && loss.is_contiguous() &&
+                  loss.scalar_type() == at::kFloat && loss.dim() == 1 && loss.numel() == tgt.numel(),
+              "xent_reduce: loss [R] float32, contiguous, on the targets' device");
+  xent_stats_check(stats, tgt, "xent_reduce");
+  DevGuard g(tgt.device());
+  CS_LAUNCH(cs_xent_reduce(loss.data_ptr<float>(), tgt.data_ptr<int64_t>(), (int)tgt.numel(), ignore_index,
+                           stats.data_ptr<double>(), cur_stream()));
+}
+
+// logits_chunk [rows, V] is overwritten with its gradient; loss / lse [R] get rows row0 .. row0 + rows - 1
+void xent_fused_(torch::Tensor logits, torch::Tensor tgt, torch::Tensor loss, torch::Tensor lse, torch::Tensor stats,
+                 int64_t row0, int64_t ignore_index, double z_loss) {
+  const char* fn = "xent_fused_";
+  check(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(1) > 0 && logits.size(1) % 8 == 0, fn,
+              ": logits [rows, V] with V % 8 == 0");
+  TORCH_CHECK(logits.size(0) <= INT_MAX && logits.size(1) <= INT_MAX, fn, ": dimension too large");
+  xent_targets_check(tgt, fn);
+  TORCH_CHECK(tgt.device() == logits.device(), fn, ": targets must be on the logits' device");
+  const int64_t R = tgt.numel();
+  for (auto* t : {&loss, &lse})
+    TORCH_CHECK(t->is_cuda() && t->device() == logits.device() && t->is_contiguous() &&
+                    t->scalar_type() == at::kFloat && t->dim() == 1 && t->numel() == R,
+                fn, ": loss / lse [R] float32, contiguous, on the logits' device");
+  xent_stats_check(stats, logits, fn);
+  TORCH_CHECK(row0 >= 0 && row0 <= R && logits.size(0) <= R - row0, fn, ": rows row0 .. row0 + rows - 1 must lie in [0, R), got row0 ",
+              row0, ", rows ", logits.size(0), ", R ", R);
+  TORCH_CHECK(std::isfinite(z_loss) && z_loss >= 0.0 && z_loss <= FLT_MAX, fn,
+              ": z_loss must be a finite float >= 0, got ", z_loss);
+  check_aligned(logits, "logits");
+  DevGuard g(logits.device());
+  CS_LAUNCH(cs_xent_fused(dt_of(logits), logits.data_ptr(), tgt.data_ptr<int64_t>(), loss.data_ptr<float>(),
+                          lse.data_ptr<float>(), stats.data_ptr<double>(), (int)logits.size(0), (int)logits.size(1),
+                          (int)R, (int)row0, ignore_index, (float)z_loss, cur_stream()));
+}
+
 torch::Tensor swiglu_fwd(torch::Tensor a, torch::Tensor b) {
   check(a, "a"); check(b, "b");
   TORCH_CHECK(a.sizes() == b.sizes() && a.scalar_type() == b.scalar_type(), "swiglu: a/b mismatch");
@@ -352,6 +407,11 @@ void register_lm_ops(pybind11::module& m) {
         "softmax cross-entropy rows with an ignore index and a z-loss -> (loss, lse, stats = [sum, n_valid, inv, "
         "mean])");
   m.def("xent_bwd_masked", &xent_bwd_masked, "its backward -> dlogits (scaled by g * stats[2], read on the device)");
+  m.def("xent_count", &xent_count, "targets -> stats = [0, n_valid, inv, 0], ahead of the first chunk of the LM head");
+  m.def("xent_fused_", &xent_fused_,
+        "forward and backward of one chunk of logits in place (-> dlogits scaled by stats[2]); loss / lse rows "
+        "row0 .. row0 + rows - 1 are written");
+  m.def("xent_reduce", &xent_reduce, "stats = [sum, n_valid, inv, mean] of the full loss vector, in place");
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("rope", &rope);

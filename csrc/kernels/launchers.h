@@ -377,6 +377,17 @@ hipError_t cs_xent_fwd_masked(int dt, const void* logits, const int64_t* tgt, fl
 hipError_t cs_xent_bwd_masked(int dt, const void* logits, const int64_t* tgt, const float* lse, const float* g,
                               const double* stats, void* dlogits, int R, int V, int64_t ignore, float z,
                               hipStream_t s);
+// the chunked LM head: cs_xent_count writes stats[1] = n_valid and stats[2] = (float)(1.0 / max(n_valid, 1))
+// over all R targets (the bits cs_xent_fwd_masked's reduction writes; stats[0] = stats[3] = 0);
+// cs_xent_fused then turns a chunk of logits [rows, V] in place into its gradient
+// (softmax * (1 + 2 z lse) - onehot) * stats[2] and writes loss / lse (full-length [R] arrays) at
+// row0 .. row0 + rows - 1 with the arithmetic of cs_xent_fwd_masked, tgt being the full [R] array too;
+// cs_xent_reduce, after the last chunk, fills all four stats from the full loss vector.
+hipError_t cs_xent_count(const int64_t* tgt, int R, int64_t ignore, double* stats, hipStream_t s);
+hipError_t cs_xent_fused(int dt, void* logits, const int64_t* tgt, float* loss, float* lse, const double* stats,
+                         int rows, int V, int R, int row0, int64_t ignore, float z, hipStream_t s);
+hipError_t cs_xent_reduce(const float* loss, const int64_t* tgt, int R, int64_t ignore, double* stats,
+                          hipStream_t s);
 hipError_t cs_swiglu_fwd(int dt, const void* a, const void* b, void* out, size_t n, hipStream_t s);
 hipError_t cs_swiglu_bwd(int dt, const void* a, const void* b, const void* g, void* da, void* db, size_t n,
                          hipStream_t s);

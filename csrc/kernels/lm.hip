@@ -518,6 +518,105 @@ __global__ __launch_bounds__(256) void xent_bwd_masked_kernel(const T* __restric
   }
 }
 
+// ---- the chunked LM head (ops/lm.py linear_cross_entropy): forward and backward of one chunk of
+// rows in one launch, in place. The chunk's logits [rows, V] become their own gradient
+// (softmax * c - onehot) * stats[2], the bits xent_bwd_masked_kernel writes for g = 1; loss / lse are
+// the full-length [R] arrays and the chunk's rows are row0 .. row0 + rows - 1 of them (and of tgt),
+// written with the arithmetic of xent_fwd_masked_kernel. stats[2] = 1 / max(n_valid, 1) over all R
+// rows is there before the first chunk (xent_count_kernel).
+// In place: a thread overwrites in pass 2 exactly the 8-vectors it read in pass 1 (the same i), and
+// x[t] is taken from the registers of the thread whose vector holds column t before that vector is
+// stored; that thread writes the loss. A target outside [0, V) has no such thread: thread 0 writes NaN.
+template <typename T, bool ZL>
+__global__ __launch_bounds__(256) void xent_fused_kernel(T* logits, const int64_t* __restrict__ tgt,
+                                                         float* __restrict__ loss, float* __restrict__ lse,
+                                                         const double* __restrict__ stats, int V, int row0,
+                                                         int64_t ignore, float z) {
+  __shared__ float sm[4], ss[4];
+  __shared__ float sl;
+  const size_t row = (size_t)row0 + blockIdx.x;
+  T* x = logits + (size_t)blockIdx.x * V;
+  const int64_t t = tgt[row];
+  if (t == ignore) {  // uniform across the block; the row is written, its logits are not read
+    uint4* dz = reinterpret_cast<uint4*>(x);
+    const int nvec = V / (16 / (int)sizeof(T));
+    for (int i = threadIdx.x; i < nvec; i += 256) dz[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (threadIdx.x == 0) {
+      loss[row] = 0.f;
+      lse[row] = 0.f;
+    }
+    return;
+  }
+  const float l0 = xent_row_lse(x, V, sm, ss);
+  if (threadIdx.x == 0) sl = l0;
+  __syncthreads();
+  const float l = sl, scale = (float)stats[2];
+  const float c = 1.f + 2.f * z * l;  // d(lse + z lse^2) / d lse
+  float xt = 0.f;
+  bool own = false;
+  for (int i = threadIdx.x * 8; i < V; i += 256 * 8) {
+    float v[8];
+    ld8(x + i, v);
+    float4 a, b;
+    float o[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const bool hit = i + j == t;
+      if (hit) {
+        xt = v[j];
+        own = true;
+      }
+      float p = __expf(v[j] - l);
+      if (ZL) p *= c;
+      o[j] = (p - (hit ? 1.f : 0.f)) * scale;
+    }
+    a = make_float4(o[0], o[1], o[2], o[3]);
+    b = make_float4(o[4], o[5], o[6], o[7]);
+    st4(x + i, a);
+    st4(x + i + 4, b);
+  }
+  if (threadIdx.x == 0) lse[row] = l;
+  if (own) {
+    const float nll = l - xt;
+    loss[row] = z != 0.f ? nll + z * l * l : nll;
+  } else if (threadIdx.x == 0 && (t < 0 || t >= V)) {
+    loss[row] = NAN;
+  }
+}
+
+// n_valid and its reciprocal over all R targets, ahead of the first chunk: the thread-to-row layout,
+// the fixed tree and the rounding of xent_reduce_kernel, so stats[1] and stats[2] are the bits it
+// writes after the last chunk. stats[0] and stats[3] (the sum and the mean, not known yet) are set to 0.
+__global__ __launch_bounds__(kRedThreads) void xent_count_kernel(const int64_t* __restrict__ tgt, int R,
+                                                                 int64_t ignore, double* __restrict__ stats) {
+  __shared__ int rn[kRedThreads];
+  int n = 0;
+  for (int64_t base = threadIdx.x; base < R; base += kRedThreads * kRedBatch) {
+    int64_t t[kRedBatch];
+#pragma unroll
+    for (int k = 0; k < kRedBatch; ++k) {
+      const int64_t i = base + (int64_t)k * kRedThreads;
+      t[k] = i < R ? tgt[i] : ignore;
+    }
+#pragma unroll
+    for (int k = 0; k < kRedBatch; ++k) n += t[k] != ignore ? 1 : 0;
+  }
+  rn[threadIdx.x] = n;
+  __syncthreads();
+#pragma unroll
+  for (int s = kRedThreads / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) rn[threadIdx.x] += rn[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  const int nv = rn[0];
+  const float inv = (float)(1.0 / (double)(nv > 1 ? nv : 1));
+  stats[0] = 0.0;
+  stats[1] = (double)nv;
+  stats[2] = (double)inv;
+  stats[3] = 0.0;
+}
+
 bool use4(int D) { return D % 4 == 0 && D / 4 <= 256 * kMaxQ; }
 
 }  // namespace
@@ -640,6 +739,34 @@ hipError_t cs_xent_bwd_masked(int dt, const void* logits, const int64_t* tgt, co
   } else {
     CS_DT_DISPATCH(dt, hipLaunchKernelGGL((xent_bwd_masked_kernel<T, false>), dim3(R), dim3(256), 0, s,
                                           (const T*)logits, tgt, lse, g, stats, (T*)dlogits, V, ignore, z));
+  }
+  return hipGetLastError();
+}
+
+hipError_t cs_xent_count(const int64_t* tgt, int R, int64_t ignore, double* stats, hipStream_t s) {
+  if (R < 0 || stats == nullptr) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(xent_count_kernel, dim3(1), dim3(kRedThreads), 0, s, tgt, R, ignore, stats);
+  return hipGetLastError();
+}
+
+hipError_t cs_xent_reduce(const float* loss, const int64_t* tgt, int R, int64_t ignore, double* stats,
+                          hipStream_t s) {
+  if (R < 0 || stats == nullptr) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(xent_reduce_kernel, dim3(1), dim3(kRedThreads), 0, s, loss, tgt, R, ignore, stats);
+  return hipGetLastError();
+}
+
+hipError_t cs_xent_fused(int dt, void* logits, const int64_t* tgt, float* loss, float* lse, const double* stats,
+                         int rows, int V, int R, int row0, int64_t ignore, float z, hipStream_t s) {
+  if (rows < 0 || row0 < 0 || (int64_t)row0 + rows > R || V <= 0 || V % 8 != 0 || !(z >= 0.f) || stats == nullptr)
+    return hipErrorInvalidValue;
+  if (rows == 0) return hipSuccess;
+  if (z != 0.f) {
+    CS_DT_DISPATCH(dt, hipLaunchKernelGGL((xent_fused_kernel<T, true>), dim3(rows), dim3(256), 0, s, (T*)logits, tgt,
+                                          loss, lse, stats, V, row0, ignore, z));
+  } else {
+    CS_DT_DISPATCH(dt, hipLaunchKernelGGL((xent_fused_kernel<T, false>), dim3(rows), dim3(256), 0, s, (T*)logits, tgt,
+                                          loss, lse, stats, V, row0, ignore, z));
   }
   return hipGetLastError();
 }
