@@ -15,7 +15,8 @@ deterministic backward, bf16, head dim 64/128) in ``ops.attention`` — called o
 [B, S, H, D] projections directly, no transposes. The projection GEMMs are plain library
 GEMMs (hipBLASLt), run on bf16 copies of the fp32 master weights that the fused SGD pass
 rewrites (``ops.lm.ShadowLinear``): no per-step weight casts, fp32 weight gradients straight out
-of the GEMM.
+of the GEMM. With ``Llama.fused_residual`` (opt-in) every residual add after the first norm runs
+inside the RMSNorm that follows it (``ops.lm.add_rms_norm``).
 """
 from __future__ import annotations
 
@@ -69,6 +70,10 @@ class RMSNorm(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return _ops().rms_norm(x, self.weight, self.eps)
+
+    def add(self, x: torch.Tensor, delta: torch.Tensor) -> tuple:
+        """``(h, self(h))`` with ``h = x + delta``: the residual add fused into this norm"""
+        return _ops().add_rms_norm(x, delta, self.weight, self.eps)
 
 
 def rope_tables(seq: int, head_dim: int, theta: float, device) -> tuple:
@@ -128,6 +133,15 @@ class Block(nn.Module):
         x = x + self.attention(self.attention_norm(x), cos, sin, doc)
         return x + self.feed_forward(self.ffn_norm(x))
 
+    def forward_fused(self, h, y, next_norm: RMSNorm, cos, sin, doc=None) -> tuple:
+        """The same block with each residual add fused into the norm that follows it
+        (``ops.lm.add_rms_norm``). ``h``: the stream entering the block, ``y``: its ``attention_norm``,
+        already computed (by the previous block, or plainly for the first one); ``next_norm``: the norm
+        that reads this block's output, the next block's ``attention_norm`` or the model's final norm.
+        Returns the stream leaving the block and its ``next_norm``."""
+        h, y = self.ffn_norm.add(h, self.attention(y, cos, sin, doc))
+        return next_norm.add(h, self.feed_forward(y))
+
 
 class Llama(nn.Module):
     def __init__(self, cfg: LlamaConfig):
@@ -148,6 +162,9 @@ class Llama(nn.Module):
             nn.init.normal_(blk.attention.wo.weight, 0.0, std / math.sqrt(2 * cfg.n_layers))
             nn.init.normal_(blk.feed_forward.w2.weight, 0.0, std / math.sqrt(2 * cfg.n_layers))
         self._rope = None
+        # opt-in: fuse every residual add into the RMSNorm that follows it (ops.lm.add_rms_norm);
+        # same parameters and state_dict, same results (TorchTrainer(fused_residual=True) sets it)
+        self.fused_residual = False
 
     def _tables(self, S: int, device):
         if self._rope is None or self._rope[0].shape[0] < S or self._rope[0].device != device:
@@ -174,6 +191,18 @@ class Llama(nn.Module):
         S = tokens.shape[1]
         cos, sin = self._tables(S, tokens.device)
         h = self.tok_embeddings(tokens)
+        if self.fused_residual and len(self.layers) > 0:
+            doc = None
+            if doc_ids is not None:
+                from ..ops.attention import doc_bounds
+                doc = doc_bounds(doc_ids)
+            # the first norm is a plain one; every residual add after it runs inside the norm that
+            # follows it (2 * n_layers fused sites), the last inside the final norm
+            y = self.layers[0].attention_norm(h)
+            norms = [blk.attention_norm for blk in self.layers[1:]] + [self.norm]
+            for blk, nxt in zip(self.layers, norms):
+                h, y = blk.forward_fused(h, y, nxt, cos, sin, doc)
+            return y
         if doc_ids is None:
             for blk in self.layers:
                 h = blk(h, cos, sin)

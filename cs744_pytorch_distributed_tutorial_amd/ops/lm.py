@@ -21,6 +21,12 @@ def rms_norm_ref(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
     return y.to(x.dtype)
 
 
+def add_rms_norm_ref(x: torch.Tensor, delta: torch.Tensor, w: torch.Tensor, eps: float):
+    """(h, y): the residual sum ``h = x + delta`` and its RMSNorm"""
+    h = x + delta
+    return h, rms_norm_ref(h, w, eps)
+
+
 def swiglu_ref(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return (torch.nn.functional.silu(a.float()) * b.float()).to(a.dtype)
 
@@ -59,6 +65,42 @@ class _RMSNorm(torch.autograd.Function):
             gy = gy.to(x.dtype)  # the scalar kernels read the gradient in x's dtype
         dx, dw = native.C().rmsnorm_bwd(x, _aligned(w), rstd, _aligned(gy))
         return dx, dw, None, None
+
+
+class _AddRMSNorm(torch.autograd.Function):
+    """(h, y) = (x + delta, rms_norm(x + delta)) in one pass; the backward adds the gradient of ``h``
+    to the norm's ``dx`` in the pass that computes it, and writes the copy in ``delta``'s dtype (the
+    bf16 branch under an fp32 stream) alongside."""
+
+    @staticmethod
+    def forward(ctx, x, delta, w, eps, out_bf16):
+        ctx.set_materialize_grads(False)  # an unused output's gradient arrives as None, not as zeros
+        ctx.delta_dtype = delta.dtype
+        if delta.dtype != x.dtype and not native.C().rmsnorm_vec4(x.shape[-1]):
+            delta = delta.to(x.dtype)  # the scalar kernels read every operand in the stream's dtype
+        h, y, rstd = native.C().add_rmsnorm_fwd(_aligned(x), _aligned(delta), _aligned(w), eps, out_bf16)
+        ctx.save_for_backward(h, w, rstd)
+        return h, y
+
+    @staticmethod
+    def backward(ctx, gh, gy):
+        h, w, rstd = ctx.saved_tensors
+        need_dx, need_dd = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if gy is None:  # only h was used: the add alone
+            if gh is None:
+                return None, None, None, None, None
+            return gh if need_dx else None, gh.to(ctx.delta_dtype) if need_dd else None, None, None, None
+        vec4 = native.C().rmsnorm_vec4(h.shape[-1])
+        if gy.dtype != h.dtype and not vec4:
+            gy = gy.to(h.dtype)  # the scalar kernels read the gradient in the stream's dtype
+        if gh is not None:
+            gh = _aligned(gh.to(h.dtype))
+        # same dtype: one stored gradient serves x and delta; the scalar kernels store the stream's only
+        ddt = ctx.delta_dtype if vec4 else h.dtype
+        dx, dd, dw = native.C().add_rmsnorm_bwd(h, _aligned(w), rstd, _aligned(gy), gh, ddt, need_dx, need_dd)
+        if dd is not None and dd.dtype != ctx.delta_dtype:
+            dd = dd.to(ctx.delta_dtype)
+        return dx, dd, dw, None, None
 
 
 class _SwiGLU(torch.autograd.Function):
@@ -101,6 +143,25 @@ def rms_norm(x: torch.Tensor, w: torch.Tensor, eps: float = 1e-5) -> torch.Tenso
                     and native.C().rmsnorm_vec4(x.shape[-1]))  # the scalar kernels (D % 4, D > 8192) keep x's dtype
         return _RMSNorm.apply(x, w, eps, out_bf16)
     return rms_norm_ref(x, w, eps)
+
+
+def add_rms_norm(x: torch.Tensor, delta: torch.Tensor, w: torch.Tensor, eps: float = 1e-5):
+    """``(h, y)`` with ``h = x + delta`` (the residual stream after a branch) and ``y = rms_norm(h, w, eps)``
+    (what the next branch reads), as one gfx950 pass forward and one backward: ``h`` is written once
+    and not read back, and the backward adds the gradient of ``h`` to the norm's input gradient where
+    it computes it, writing the bf16 copy for a bf16 branch in the same pass. ``h`` has ``x``'s dtype
+    and the statistics are those of ``h`` as stored, so the result is ``rms_norm(x + delta)`` bit for bit;
+    ``y`` follows ``rms_norm``'s dtype rule (bf16 under bf16 autocast on the 4-wide path).
+
+    GPU fp32 / bf16 tensors, ``delta`` in ``x``'s dtype or bf16 on an fp32 stream, run the kernels;
+    anything else (CPU, other dtypes, an fp32 ``delta`` on a bf16 stream, where torch's sum is fp32)
+    runs ``add_rms_norm_ref``."""
+    if (_native_ok(x, delta, w) and x.shape == delta.shape and w.numel() > 0
+            and (delta.dtype == x.dtype or x.dtype == torch.float32)):
+        out_bf16 = (torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16
+                    and native.C().rmsnorm_vec4(x.shape[-1]))  # the same rule as rms_norm
+        return _AddRMSNorm.apply(x, delta, w, eps, out_bf16)
+    return add_rms_norm_ref(x, delta, w, eps)
 
 
 def swiglu(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:

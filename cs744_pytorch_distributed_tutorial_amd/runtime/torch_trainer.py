@@ -103,7 +103,8 @@ class TorchTrainer:
                  lr: float = 0.1, momentum: float = 0.9, weight_decay: float = 1e-4, seed: int = 5000,
                  seq_len: int = 0, fused_sgd: bool = True, optimizer: Optional[str] = None, betas=(0.9, 0.95),
                  eps: float = 1e-8, max_grad_norm: Optional[float] = None, doc_len: Optional[int] = None,
-                 loss_mask: Optional[str] = None, z_loss: Optional[float] = None, fused_head: Optional[bool] = None):
+                 loss_mask: Optional[str] = None, z_loss: Optional[float] = None, fused_head: Optional[bool] = None,
+                 fused_residual: Optional[bool] = None):
         """``doc_len``: pack documents of about that many tokens into every row of the synthetic token
         pool (``SyntheticBatches``) and train with document-masked attention: ``step()`` derives the
         document of every token from the EOS tokens of its input, the way real packed data would be
@@ -123,6 +124,11 @@ class TorchTrainer:
         built whole; ``step()`` hands targets, ignore index and z-loss to the model and ``evaluate()``
         uses ``ops.lm.linear_cross_entropy_sums``. ``None`` takes ``CS744_FUSED_HEAD=1`` if set, else off.
         LM models only. ``CS_LM_HEAD_CHUNK_MB`` sets the chunk size.
+
+        ``fused_residual``: fuse every residual add of the decoder blocks into the RMSNorm that follows
+        it (``ops.lm.add_rms_norm``; sets ``Llama.fused_residual``): same parameters, same results, less
+        traffic on the residual stream. ``None`` takes ``CS744_FUSED_RESIDUAL=1`` if set, else off. LM
+        models only.
 
         ``optimizer``: ``"sgd"`` (momentum SGD, the default) or ``"adamw"`` (AdamW with decoupled weight
         decay on the parameters with ``dim() >= 2`` only, and global-norm gradient clipping at
@@ -214,6 +220,14 @@ class TorchTrainer:
         if fused_head and not self.is_lm:
             raise ValueError(f"fused_head (the chunked linear + cross-entropy head) is for the LM models, not {model!r}")
         self.fused_head = bool(fused_head)
+        if fused_residual is None:
+            fused_residual = os.environ.get("CS744_FUSED_RESIDUAL", "0") == "1"
+        if fused_residual and not self.is_lm:
+            raise ValueError(f"fused_residual (the residual add fused into the RMSNorm) is for the LM models, "
+                             f"not {model!r}")
+        self.fused_residual = bool(fused_residual)
+        if self.is_lm:
+            self.module.fused_residual = self.fused_residual
         if self.is_lm:
             self.eos_id = self.module.cfg.eos_id
             self.data = SyntheticBatches("tokens", batch_size, device, seq=seq_len or self.module.max_seq,

@@ -68,6 +68,80 @@ std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor x, torch::Tensor w, torch::
   return {dx, dw};
 }
 
+// h = x + delta in x's dtype, y = rms_norm(h, w) (bf16 when out_bf16), rstd of h -> {h, y, rstd}
+std::vector<torch::Tensor> add_rmsnorm_fwd(torch::Tensor x, torch::Tensor delta, torch::Tensor w, double eps,
+                                           bool out_bf16) {
+  check(x, "x"); check(delta, "delta"); check(w, "w");
+  const int64_t D = w.numel();
+  TORCH_CHECK(D > 0 && D <= INT_MAX && x.dim() >= 1 && x.size(-1) == D, "add_rmsnorm: last dim must match the weight");
+  TORCH_CHECK(delta.sizes() == x.sizes(), "add_rmsnorm: x and delta must have one shape");
+  const int64_t rows = x.numel() / D;
+  TORCH_CHECK(rows <= INT_MAX, "add_rmsnorm: too many rows");
+  const bool vec4 = cs_rmsnorm_vec4((int)D);
+  TORCH_CHECK(!out_bf16 || x.scalar_type() == at::kBFloat16 || vec4,
+              "add_rmsnorm: bf16 output of fp32 input needs D % 4 == 0 and D <= 8192");
+  TORCH_CHECK(delta.scalar_type() == x.scalar_type() || vec4,
+              "add_rmsnorm: mixed dtypes need D % 4 == 0 and D <= 8192");
+  DevGuard g(x.device());
+  auto h = torch::empty_like(x);
+  auto y = out_bf16 ? torch::empty_like(x, x.options().dtype(at::kBFloat16)) : torch::empty_like(x);
+  auto rstd = torch::empty({rows}, x.options().dtype(at::kFloat));
+  if (rows == 0) return {h, y, rstd};
+  if (vec4) {
+    check_aligned(x, "x"); check_aligned(delta, "delta"); check_aligned(w, "w");
+    check_aligned(h, "h"); check_aligned(y, "y");
+  }
+  CS_LAUNCH(cs_add_rmsnorm_fwd(dt_of(x), dt_of(delta), dt_of(w), dt_of(y), x.data_ptr(), delta.data_ptr(),
+                               w.data_ptr(), h.data_ptr(), y.data_ptr(), rstd.data_ptr<float>(), (int)rows, (int)D,
+                               (float)eps, cur_stream()));
+  return {h, y, rstd};
+}
+
+// d = gh + (the norm's input gradient of gy), gh absent = zero and not read -> {dx, ddelta, dw}: dx = d in h's
+// dtype when need_dx, ddelta = d in delta_dtype when need_ddelta (one tensor serves both when the dtypes
+// agree), an output nobody asked for is undefined (None) and not stored
+std::vector<torch::Tensor> add_rmsnorm_bwd(torch::Tensor h, torch::Tensor w, torch::Tensor rstd, torch::Tensor gy,
+                                           c10::optional<torch::Tensor> gh, at::ScalarType delta_dtype, bool need_dx,
+                                           bool need_ddelta) {
+  check(h, "h"); check(w, "w"); check(rstd, "rstd"); check(gy, "gy");
+  const int64_t D = w.numel();
+  TORCH_CHECK(D > 0 && D <= INT_MAX && h.dim() >= 1 && h.size(-1) == D, "add_rmsnorm_bwd: last dim must match the weight");
+  const int64_t rows = h.numel() / D;
+  TORCH_CHECK(rows <= INT_MAX && gy.sizes() == h.sizes() && rstd.numel() == rows &&
+              rstd.scalar_type() == at::kFloat, "add_rmsnorm_bwd: shapes");
+  TORCH_CHECK(delta_dtype == at::kFloat || delta_dtype == at::kBFloat16, "add_rmsnorm_bwd: delta dtype float32 / bfloat16");
+  const bool has_gh = gh.has_value() && gh->defined();
+  if (has_gh) {
+    check(*gh, "gh");
+    TORCH_CHECK(gh->sizes() == h.sizes() && gh->scalar_type() == h.scalar_type(), "add_rmsnorm_bwd: gh must match h");
+  }
+  const bool vec4 = cs_rmsnorm_vec4((int)D);
+  TORCH_CHECK((gy.scalar_type() == h.scalar_type() && delta_dtype == h.scalar_type()) || vec4,
+              "add_rmsnorm_bwd: mixed dtypes need D % 4 == 0 and D <= 8192");
+  DevGuard g(h.device());
+  const bool same = delta_dtype == h.scalar_type();
+  torch::Tensor dx, dd;
+  if (need_dx || (need_ddelta && same)) dx = torch::empty_like(h);
+  if (need_ddelta && !same) dd = torch::empty_like(h, h.options().dtype(delta_dtype));
+  // no rows: the weight gradient is the empty sum
+  auto dw = rows == 0 ? torch::zeros_like(w) : torch::empty_like(w);
+  if (rows > 0) {
+    auto part = torch::empty({(int64_t)cs_rmsnorm_bwd_partials((int)rows, (int)D), D}, h.options().dtype(at::kFloat));
+    if (vec4) {
+      check_aligned(h, "h"); check_aligned(w, "w"); check_aligned(gy, "gy"); check_aligned(dw, "dw");
+      check_aligned(part, "part");
+      if (has_gh) check_aligned(*gh, "gh");
+      if (dx.defined()) check_aligned(dx, "dx");
+      if (dd.defined()) check_aligned(dd, "ddelta");
+    }
+    CS_LAUNCH(cs_add_rmsnorm_bwd(dt_of(h), dt_of(w), dt_of(gy), dd.defined() ? dt_of(dd) : dt_of(h), h.data_ptr(),
+                                 w.data_ptr(), rstd.data_ptr<float>(), gy.data_ptr(), has_gh ? gh->data_ptr() : nullptr,
+                                 dx.defined() ? dx.data_ptr() : nullptr, dd.defined() ? dd.data_ptr() : nullptr,
+                                 dw.data_ptr(), part.data_ptr<float>(), (int)rows, (int)D, cur_stream()));
+  }
+  return {need_dx ? dx : torch::Tensor(), need_ddelta ? (same ? dx : dd) : torch::Tensor(), dw};
+}
+
 // logits [R, V], targets [R] int64 -> {loss_rows [R] f32, lse [R] f32}
 std::vector<torch::Tensor> xent_fwd(torch::Tensor logits, torch::Tensor tgt) {
   check(logits, "logits");
@@ -401,6 +475,10 @@ void register_lm_ops(pybind11::module& m) {
         "whether RMSNorm of width D runs the 4-wide kernels (aligned operands; mixed dtypes allowed)");
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
   m.def("rmsnorm_bwd", &rmsnorm_bwd);
+  m.def("add_rmsnorm_fwd", &add_rmsnorm_fwd, "h = x + delta, y = rms_norm(h, w) in one pass -> (h, y, rstd)");
+  m.def("add_rmsnorm_bwd", &add_rmsnorm_bwd,
+        "(h, w, rstd, gy, gh or None, delta_dtype, need_dx, need_ddelta) -> (dx, ddelta, dw): gh + the norm's input "
+        "gradient in h's dtype and in delta's, None where not asked for");
   m.def("xent_fwd", &xent_fwd, "softmax cross-entropy rows -> (loss, lse)");
   m.def("xent_bwd", &xent_bwd, "its backward -> dlogits");
   m.def("xent_fwd_masked", &xent_fwd_masked,

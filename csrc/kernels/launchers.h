@@ -361,6 +361,16 @@ hipError_t cs_rmsnorm_fwd(int dt, int wdt, int odt, const void* x, const void* w
 // part: [cs_rmsnorm_bwd_partials(rows, D)][D] fp32 scratch; dw has the weight's dtype, g dtype gdt, dx x's
 hipError_t cs_rmsnorm_bwd(int dt, int wdt, int gdt, const void* x, const void* w, const float* rstd, const void* g,
                           void* dx, void* dw, float* part, int rows, int D, hipStream_t s);
+// residual add fused into the norm: h = x + delta (x's dtype dt, rounded once), y = rms_norm(h, w) of dtype
+// odt, rstd of h as stored. delta has dtype ddt; ddt != dt and odt != dt need cs_rmsnorm_vec4(D)
+hipError_t cs_add_rmsnorm_fwd(int dt, int ddt, int wdt, int odt, const void* x, const void* delta, const void* w,
+                              void* h, void* y, float* rstd, int rows, int D, float eps, hipStream_t s);
+// d = gh + (the norm's dx of g), stored to dx in h's dtype dt and / or to ddelta in dtype ddt; gh (dtype dt),
+// dx and ddelta may each be null (gh: no gradient reaches h itself; dx, ddelta: not wanted). dw and part as
+// cs_rmsnorm_bwd. ddelta and gdt != dt need cs_rmsnorm_vec4(D)
+hipError_t cs_add_rmsnorm_bwd(int dt, int wdt, int gdt, int ddt, const void* h, const void* w, const float* rstd,
+                              const void* g, const void* gh, void* dx, void* ddelta, void* dw, float* part, int rows,
+                              int D, hipStream_t s);
 // softmax cross-entropy, logits [R, V] fp32/bf16 with V % 8 == 0, targets in [0, V): per-row loss and
 // log-sum-exp; backward dlogits = (softmax - onehot) * g[0] * inv_n in the logits' dtype
 hipError_t cs_xent_fwd(int dt, const void* logits, const int64_t* tgt, float* loss, float* lse, int R, int V,

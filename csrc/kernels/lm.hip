@@ -22,6 +22,16 @@ __device__ __forceinline__ void st(__hip_bfloat16* p, size_t i, float v) { p[i] 
 
 constexpr int kRowsPerBlock = 8;
 
+// ---- the RMSNorm row arithmetic, one definition for the plain kernels and for the ones that fuse the
+// residual add (add_rmsnorm_*): the same expressions over the same values give the same bits
+__device__ __forceinline__ float rms_rstd(float ss, int D, float eps) { return rsqrtf(ss / (float)D + eps); }
+__device__ __forceinline__ float rms_scale(float x, float r, float w) { return x * r * w; }
+__device__ __forceinline__ float rms_dot(float w, float g, float x) { return w * g * x; }
+// c = r^3 dot / D;  dx_j = r*w_j*g_j - c x_j;  dw partial_j += g_j x_j r
+__device__ __forceinline__ float rms_c(float r, float dot, int D) { return r * r * r * dot / (float)D; }
+__device__ __forceinline__ float rms_dx(float r, float c, float w, float g, float x) { return r * w * g - c * x; }
+__device__ __forceinline__ float rms_dw(float g, float x, float r) { return g * x * r; }
+
 template <typename T, typename W>
 __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const T* __restrict__ x, const W* __restrict__ w,
                                                           T* __restrict__ y, float* __restrict__ rstd, int rows,
@@ -36,10 +46,10 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const T* __restrict__ 
     ss += v * v;
   }
   ss = cs::block_sum(ss, red);
-  const float r = rsqrtf(ss / (float)D + eps);
+  const float r = rms_rstd(ss, D, eps);
   if (threadIdx.x == 0) rstd[row] = r;
   T* yr = y + (size_t)row * D;
-  for (int i = threadIdx.x; i < D; i += blockDim.x) st(yr, i, ld(xr, i) * r * ld(w, i));
+  for (int i = threadIdx.x; i < D; i += blockDim.x) st(yr, i, rms_scale(ld(xr, i), r, ld(w, i)));
 }
 
 // dx_j = r*w_j*g_j - (r^3/D) x_j sum_i(w_i g_i x_i);  dw partial_j = sum_rows g_j x_j r
@@ -59,14 +69,14 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const T* __restrict__ 
     const T* gr = g + (size_t)row * D;
     const float r = rstd[row];
     float dot = 0.f;
-    for (int i = threadIdx.x; i < D; i += blockDim.x) dot += ld(w, i) * ld(gr, i) * ld(xr, i);
+    for (int i = threadIdx.x; i < D; i += blockDim.x) dot += rms_dot(ld(w, i), ld(gr, i), ld(xr, i));
     dot = cs::block_sum(dot, red);
-    const float c = r * r * r * dot / (float)D;
+    const float c = rms_c(r, dot, D);
     T* dxr = dx + (size_t)row * D;
     for (int i = threadIdx.x; i < D; i += blockDim.x) {
       const float xv = ld(xr, i), gv = ld(gr, i);
-      st(dxr, i, r * ld(w, i) * gv - c * xv);
-      part[i] += gv * xv * r;  // same thread owns column i for every row: no race
+      st(dxr, i, rms_dx(r, c, ld(w, i), gv, xv));
+      part[i] += rms_dw(gv, xv, r);  // same thread owns column i for every row: no race
     }
   }
 }
@@ -88,6 +98,24 @@ __device__ __forceinline__ void st4(__hip_bfloat16* p, float4 v) {
   *reinterpret_cast<uint2*>(p) = *reinterpret_cast<const uint2*>(e);
 }
 
+__device__ __forceinline__ float rms_ss4(float4 v) { return v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w; }
+__device__ __forceinline__ float4 rms_scale4(float4 v, float r, float4 w) {
+  return make_float4(v.x * r * w.x, v.y * r * w.y, v.z * r * w.z, v.w * r * w.w);
+}
+__device__ __forceinline__ float rms_dot4(float4 w, float4 g, float4 x) {
+  return w.x * g.x * x.x + w.y * g.y * x.y + w.z * g.z * x.z + w.w * g.w * x.w;
+}
+__device__ __forceinline__ float4 rms_dx4(float r, float c, float4 w, float4 g, float4 x) {
+  return make_float4(r * w.x * g.x - c * x.x, r * w.y * g.y - c * x.y, r * w.z * g.z - c * x.z,
+                     r * w.w * g.w - c * x.w);
+}
+__device__ __forceinline__ void rms_dw4(float4& acc, float4 g, float4 x, float r) {
+  acc.x += g.x * x.x * r;
+  acc.y += g.y * x.y * r;
+  acc.z += g.z * x.z * r;
+  acc.w += g.w * x.w * r;
+}
+
 template <typename T, typename W, typename O>
 __global__ __launch_bounds__(256) void rmsnorm_fwd4_kernel(const T* __restrict__ x, const W* __restrict__ w,
                                                            O* __restrict__ y, float* __restrict__ rstd, int rows,
@@ -102,19 +130,18 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd4_kernel(const T* __restrict__
     const int q = threadIdx.x + k * 256;
     if (q < DQ) {
       v[k] = ld4(xr + 4 * q);
-      ss += v[k].x * v[k].x + v[k].y * v[k].y + v[k].z * v[k].z + v[k].w * v[k].w;
+      ss += rms_ss4(v[k]);
     }
   }
   ss = cs::block_sum(ss, red);
-  const float r = rsqrtf(ss / (float)D + eps);
+  const float r = rms_rstd(ss, D, eps);
   if (threadIdx.x == 0) rstd[row] = r;
   O* yr = y + (size_t)row * D;
 #pragma unroll
   for (int k = 0; k < kMaxQ; ++k) {
     const int q = threadIdx.x + k * 256;
     if (q < DQ) {
-      const float4 wv = ld4(w + 4 * q);
-      st4(yr + 4 * q, make_float4(v[k].x * r * wv.x, v[k].y * r * wv.y, v[k].z * r * wv.z, v[k].w * r * wv.w));
+      st4(yr + 4 * q, rms_scale4(v[k], r, ld4(w + 4 * q)));
     }
   }
 }
@@ -148,24 +175,19 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd4_kernel(const T* __restrict__
       if (q < DQ) {
         xv[k] = ld4(xr + 4 * q);
         gv[k] = ld4(gr + 4 * q);
-        dot += wv[k].x * gv[k].x * xv[k].x + wv[k].y * gv[k].y * xv[k].y + wv[k].z * gv[k].z * xv[k].z +
-               wv[k].w * gv[k].w * xv[k].w;
+        dot += rms_dot4(wv[k], gv[k], xv[k]);
       }
     }
     dot = cs::block_sum(dot, red);
     const float r = rstd[row];
-    const float c = r * r * r * dot / (float)D;
+    const float c = rms_c(r, dot, D);
     T* dxr = dx + (size_t)row * D;
 #pragma unroll
     for (int k = 0; k < kMaxQ; ++k) {
       const int q = threadIdx.x + k * 256;
       if (q < DQ) {
-        st4(dxr + 4 * q, make_float4(r * wv[k].x * gv[k].x - c * xv[k].x, r * wv[k].y * gv[k].y - c * xv[k].y,
-                                     r * wv[k].z * gv[k].z - c * xv[k].z, r * wv[k].w * gv[k].w - c * xv[k].w));
-        acc[k].x += gv[k].x * xv[k].x * r;
-        acc[k].y += gv[k].y * xv[k].y * r;
-        acc[k].z += gv[k].z * xv[k].z * r;
-        acc[k].w += gv[k].w * xv[k].w * r;
+        st4(dxr + 4 * q, rms_dx4(r, c, wv[k], gv[k], xv[k]));
+        rms_dw4(acc[k], gv[k], xv[k], r);
       }
     }
   }
@@ -210,6 +232,173 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ p
   float s = 0.f;
   for (int p = 0; p < P; ++p) s += part[(size_t)p * D + i];
   st(dw, i, s);
+}
+
+// ---- residual add fused into the norm that follows it: h = x + delta, y = rms_norm(h, w).
+// The sum is one fp32 add rounded once to h's dtype, and the statistics and y are those of h as
+// stored, so the pair is rms_norm_fwd(x + delta) bit for bit and the backward, which re-reads the
+// stored h, differentiates the function that ran.
+__device__ __forceinline__ float as_stored(const float*, float v) { return v; }
+__device__ __forceinline__ float as_stored(const __hip_bfloat16*, float v) {
+  return __bfloat162float(__float2bfloat16(v));
+}
+template <typename T>
+__device__ __forceinline__ float4 as_stored4(const T* p, float4 v) {
+  return make_float4(as_stored(p, v.x), as_stored(p, v.y), as_stored(p, v.z), as_stored(p, v.w));
+}
+// an add that stays an add (__fadd_rn, and operands that are never products: a loaded value and a
+// finished result), so that the sum has the bits of the two-kernel composition
+__device__ __forceinline__ float4 add4_rn(float4 a, float4 b) {
+  return make_float4(__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y), __fadd_rn(a.z, b.z), __fadd_rn(a.w, b.w));
+}
+
+// scalar path: x, delta, h, y of one dtype
+template <typename T, typename W>
+__global__ __launch_bounds__(256) void add_rmsnorm_fwd_kernel(const T* __restrict__ x, const T* __restrict__ delta,
+                                                              const W* __restrict__ w, T* __restrict__ h,
+                                                              T* __restrict__ y, float* __restrict__ rstd, int rows,
+                                                              int D, float eps) {
+  __shared__ float red[16];
+  const int row = blockIdx.x;
+  if (row >= rows) return;
+  const T* xr = x + (size_t)row * D;
+  const T* dr = delta + (size_t)row * D;
+  T* hr = h + (size_t)row * D;
+  float ss = 0.f;
+  for (int i = threadIdx.x; i < D; i += blockDim.x) {
+    const float v = as_stored(hr, __fadd_rn(ld(xr, i), ld(dr, i)));
+    st(hr, i, v);
+    ss += v * v;
+  }
+  ss = cs::block_sum(ss, red);
+  const float r = rms_rstd(ss, D, eps);
+  if (threadIdx.x == 0) rstd[row] = r;
+  T* yr = y + (size_t)row * D;
+  // every thread re-reads the elements of h that it wrote itself
+  for (int i = threadIdx.x; i < D; i += blockDim.x) st(yr, i, rms_scale(ld(hr, i), r, ld(w, i)));
+}
+
+// scalar path: g, gh, dx in h's dtype; gh == nullptr: no gradient reaches h but the norm's;
+// dx == nullptr: only the weight gradient is wanted
+template <typename T, typename W>
+__global__ __launch_bounds__(256) void add_rmsnorm_bwd_kernel(const T* __restrict__ h, const W* __restrict__ w,
+                                                              const float* __restrict__ rstd, const T* __restrict__ g,
+                                                              const T* __restrict__ gh, T* __restrict__ dx,
+                                                              float* __restrict__ dw_part, int rows, int D) {
+  __shared__ float red[16];
+  const int r0 = blockIdx.x * kRowsPerBlock;
+  float* part = dw_part + (size_t)blockIdx.x * D;
+  for (int i = threadIdx.x; i < D; i += blockDim.x) part[i] = 0.f;
+  for (int rr = 0; rr < kRowsPerBlock; ++rr) {
+    const int row = r0 + rr;
+    if (row >= rows) break;
+    const T* xr = h + (size_t)row * D;
+    const T* gr = g + (size_t)row * D;
+    const float r = rstd[row];
+    float dot = 0.f;
+    for (int i = threadIdx.x; i < D; i += blockDim.x) dot += rms_dot(ld(w, i), ld(gr, i), ld(xr, i));
+    dot = cs::block_sum(dot, red);
+    const float c = rms_c(r, dot, D);
+    for (int i = threadIdx.x; i < D; i += blockDim.x) {
+      const float xv = ld(xr, i), gv = ld(gr, i);
+      float d = rms_dx(r, c, ld(w, i), gv, xv);
+      if (gh) d = __fadd_rn(ld(gh, (size_t)row * D + i), d);
+      if (dx) st(dx, (size_t)row * D + i, d);
+      part[i] += rms_dw(gv, xv, r);  // same thread owns column i for every row: no race
+    }
+  }
+}
+
+// 4-wide: x (and h) of dtype T, delta of dtype Dl, y of dtype O
+template <typename T, typename Dl, typename W, typename O>
+__global__ __launch_bounds__(256) void add_rmsnorm_fwd4_kernel(const T* __restrict__ x, const Dl* __restrict__ delta,
+                                                               const W* __restrict__ w, T* __restrict__ h,
+                                                               O* __restrict__ y, float* __restrict__ rstd, int rows,
+                                                               int D, float eps) {
+  __shared__ float red[16];
+  const int row = blockIdx.x, DQ = D >> 2;
+  const T* xr = x + (size_t)row * D;
+  const Dl* dr = delta + (size_t)row * D;
+  T* hr = h + (size_t)row * D;
+  float4 v[kMaxQ];
+  float ss = 0.f;
+#pragma unroll
+  for (int k = 0; k < kMaxQ; ++k) {
+    const int q = threadIdx.x + k * 256;
+    if (q < DQ) {
+      v[k] = as_stored4(hr, add4_rn(ld4(xr + 4 * q), ld4(dr + 4 * q)));
+      st4(hr + 4 * q, v[k]);
+      ss += rms_ss4(v[k]);
+    }
+  }
+  ss = cs::block_sum(ss, red);
+  const float r = rms_rstd(ss, D, eps);
+  if (threadIdx.x == 0) rstd[row] = r;
+  O* yr = y + (size_t)row * D;
+#pragma unroll
+  for (int k = 0; k < kMaxQ; ++k) {
+    const int q = threadIdx.x + k * 256;
+    if (q < DQ) st4(yr + 4 * q, rms_scale4(v[k], r, ld4(w + 4 * q)));
+  }
+}
+
+// 4-wide: kRows4 rows per block and the dw partials exactly as rmsnorm_bwd4_kernel; d = gh + dx of the
+// norm, stored in h's dtype (dx) and / or in delta's (dd) where those are wanted
+template <typename T, typename W, typename G, typename Dd>
+__global__ __launch_bounds__(256) void add_rmsnorm_bwd4_kernel(const T* __restrict__ h, const W* __restrict__ w,
+                                                               const float* __restrict__ rstd, const G* __restrict__ g,
+                                                               const T* __restrict__ gh, T* __restrict__ dx,
+                                                               Dd* __restrict__ dd, float* __restrict__ dw_part,
+                                                               int rows, int D) {
+  __shared__ float red[16];
+  const int DQ = D >> 2;
+  float4 wv[kMaxQ], acc[kMaxQ];
+#pragma unroll
+  for (int k = 0; k < kMaxQ; ++k) {
+    const int q = threadIdx.x + k * 256;
+    wv[k] = q < DQ ? ld4(w + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+    acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  const int r0 = blockIdx.x * kRows4;
+  for (int rr = 0; rr < kRows4; ++rr) {
+    const int row = r0 + rr;
+    if (row >= rows) break;  // uniform across the block
+    const T* xr = h + (size_t)row * D;
+    const G* gr = g + (size_t)row * D;
+    const size_t ro = (size_t)row * D;
+    float4 xv[kMaxQ], gv[kMaxQ], hv[kMaxQ];
+    float dot = 0.f;
+#pragma unroll
+    for (int k = 0; k < kMaxQ; ++k) {
+      const int q = threadIdx.x + k * 256;
+      if (q < DQ) {
+        xv[k] = ld4(xr + 4 * q);
+        gv[k] = ld4(gr + 4 * q);
+        if (gh) hv[k] = ld4(gh + ro + 4 * q);  // in flight across the reduction, not issued behind it
+        dot += rms_dot4(wv[k], gv[k], xv[k]);
+      }
+    }
+    dot = cs::block_sum(dot, red);
+    const float r = rstd[row];
+    const float c = rms_c(r, dot, D);
+#pragma unroll
+    for (int k = 0; k < kMaxQ; ++k) {
+      const int q = threadIdx.x + k * 256;
+      if (q < DQ) {
+        float4 d = rms_dx4(r, c, wv[k], gv[k], xv[k]);
+        if (gh) d = add4_rn(hv[k], d);
+        if (dx) st4(dx + ro + 4 * q, d);
+        if (dd) st4(dd + ro + 4 * q, d);
+        rms_dw4(acc[k], gv[k], xv[k], r);
+      }
+    }
+  }
+  float* part = dw_part + (size_t)blockIdx.x * D;
+#pragma unroll
+  for (int k = 0; k < kMaxQ; ++k) {
+    const int q = threadIdx.x + k * 256;
+    if (q < DQ) st4(part + 4 * q, acc[k]);
+  }
 }
 
 __device__ __forceinline__ float sigmoidf(float a) { return 1.f / (1.f + __expf(-a)); }
@@ -697,6 +886,47 @@ hipError_t cs_rmsnorm_bwd(int dt, int wdt, int gdt, const void* x, const void* w
     hipLaunchKernelGGL((colsum_kernel<__hip_bfloat16>), dim3((D + 255) / 256), dim3(256), 0, s, part, P, D,
                        (__hip_bfloat16*)dw);
   }
+  return hipGetLastError();
+}
+
+hipError_t cs_add_rmsnorm_fwd(int dt, int ddt, int wdt, int odt, const void* x, const void* delta, const void* w,
+                              void* h, void* y, float* rstd, int rows, int D, float eps, hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  if (D <= 0) return hipErrorInvalidValue;
+  if (use4(D)) {
+    CS_DT_DISPATCH2(dt, T, CS_DT_DISPATCH2(ddt, Dl, CS_DT_DISPATCH2(wdt, Wt, CS_DT_DISPATCH2(odt, O,
+        hipLaunchKernelGGL((add_rmsnorm_fwd4_kernel<T, Dl, Wt, O>), dim3(rows), dim3(256), 0, s, (const T*)x,
+                           (const Dl*)delta, (const Wt*)w, (T*)h, (O*)y, rstd, rows, D, eps)))));
+    return hipGetLastError();
+  }
+  if (odt != dt || ddt != dt) return hipErrorInvalidValue;  // the scalar path: one dtype for x, delta, h, y
+  CS_DT_DISPATCH2(dt, T, CS_DT_DISPATCH2(wdt, Wt,
+      hipLaunchKernelGGL((add_rmsnorm_fwd_kernel<T, Wt>), dim3(rows), dim3(256), 0, s, (const T*)x, (const T*)delta,
+                         (const Wt*)w, (T*)h, (T*)y, rstd, rows, D, eps)));
+  return hipGetLastError();
+}
+
+hipError_t cs_add_rmsnorm_bwd(int dt, int wdt, int gdt, int ddt, const void* h, const void* w, const float* rstd,
+                              const void* g, const void* gh, void* dx, void* ddelta, void* dw, float* part, int rows,
+                              int D, hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  if (D <= 0) return hipErrorInvalidValue;
+  const int P = cs_rmsnorm_bwd_partials(rows, D);
+  if (use4(D)) {
+    CS_DT_DISPATCH2(dt, T, CS_DT_DISPATCH2(wdt, Wt, CS_DT_DISPATCH2(gdt, G, CS_DT_DISPATCH2(ddt, Dd,
+        hipLaunchKernelGGL((add_rmsnorm_bwd4_kernel<T, Wt, G, Dd>), dim3(P), dim3(256), 0, s, (const T*)h,
+                           (const Wt*)w, rstd, (const G*)g, (const T*)gh, (T*)dx, (Dd*)ddelta, part, rows, D)))));
+    CS_DT_DISPATCH2(wdt, Wt, hipLaunchKernelGGL((colsum4_kernel<Wt>), dim3((D / 4 + 15) / 16), dim3(256), 0, s,
+                                                part, P, D, (Wt*)dw));
+    return hipGetLastError();
+  }
+  // the scalar path reads the gradients and writes dx in h's dtype: a second copy has nothing to add
+  if (gdt != dt || ddelta != nullptr) return hipErrorInvalidValue;
+  CS_DT_DISPATCH2(dt, T, CS_DT_DISPATCH2(wdt, Wt,
+      hipLaunchKernelGGL((add_rmsnorm_bwd_kernel<T, Wt>), dim3(P), dim3(256), 0, s, (const T*)h, (const Wt*)w, rstd,
+                         (const T*)g, (const T*)gh, (T*)dx, part, rows, D)));
+  CS_DT_DISPATCH2(wdt, Wt, hipLaunchKernelGGL((colsum_kernel<Wt>), dim3((D + 255) / 256), dim3(256), 0, s, part, P,
+                                              D, (Wt*)dw));
   return hipGetLastError();
 }
 
