@@ -15,13 +15,14 @@ deterministic backward, bf16, head dim 64/128) in ``ops.attention`` — called o
 [B, S, H, D] projections directly, no transposes. The projection GEMMs are plain library
 GEMMs (hipBLASLt), run on bf16 copies of the fp32 master weights that the fused SGD pass
 rewrites (``ops.lm.ShadowLinear``): no per-step weight casts, fp32 weight gradients straight out
-of the GEMM. With ``Llama.fused_residual`` (opt-in) every residual add after the first norm runs
+of the GEMM. With ``LlamaConfig.qk_norm`` (opt-in) q and k get a per-head RMSNorm fused with their RoPE
+(``ops.lm.qk_norm_rope``). With ``Llama.fused_residual`` (opt-in) every residual add after the first norm runs
 inside the RMSNorm that follows it (``ops.lm.add_rms_norm``).
 """
 from __future__ import annotations
 
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 
 import torch
 import torch.nn as nn
@@ -40,6 +41,9 @@ class LlamaConfig:
     rope_theta: float = 500000.0
     norm_eps: float = 1e-5
     eos_id: int = 128001  # <|end_of_text|> of the Llama-3 vocabulary: closes a document of a packed row
+    # opt-in QK-norm (Qwen3 / Gemma 3): a per-head RMSNorm of q and k with a learned [head_dim] gain each,
+    # applied before RoPE (ops.lm.qk_norm_rope); adds attention.q_norm / k_norm to every layer
+    qk_norm: bool = False
 
 
 CONFIGS = {
@@ -91,6 +95,10 @@ class Attention(nn.Module):
         self.wk = _Linear(cfg.dim, self.nkv * self.hd, bias=False)
         self.wv = _Linear(cfg.dim, self.nkv * self.hd, bias=False)
         self.wo = _Linear(self.nh * self.hd, cfg.dim, bias=False)
+        self.qk_norm = cfg.qk_norm
+        if self.qk_norm:
+            self.q_norm = RMSNorm(self.hd, cfg.norm_eps)
+            self.k_norm = RMSNorm(self.hd, cfg.norm_eps)
 
     def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, doc=None) -> torch.Tensor:
         """``doc``: ``ops.attention.DocBounds`` of a packed batch (attention stays inside a document)."""
@@ -98,7 +106,10 @@ class Attention(nn.Module):
         q = self.wq(x).view(B, S, self.nh, self.hd)
         k = self.wk(x).view(B, S, self.nkv, self.hd)
         v = self.wv(x).view(B, S, self.nkv, self.hd)
-        q, k = _ops().rope(q, cos, sin), _ops().rope(k, cos, sin)
+        if self.qk_norm:
+            q, k = _ops().qk_norm_rope(q, k, self.q_norm.weight, self.k_norm.weight, cos, sin, self.q_norm.eps)
+        else:
+            q, k = _ops().rope(q, cos, sin), _ops().rope(k, cos, sin)
         from ..ops.attention import attention, attention_ref, native_ok
         if native_ok(q, k, v):
             o = attention(q, k, v, causal=True, doc=doc)  # [B, S, Hq, hd], gfx950 flash attention
@@ -214,17 +225,19 @@ class Llama(nn.Module):
         return self.norm(h)
 
 
-def build(name: str) -> Llama:
+def build(name: str, qk_norm: bool = False) -> Llama:
     key = name.lower().replace("_", "-")
     if key in ("llama3-8b", "llama-3-8b", "llama38b"):
         key = "llama3-8b"
     if key not in CONFIGS:
         raise ValueError(f"unknown LM config {name!r}; choose from {sorted(CONFIGS)}")
-    return Llama(CONFIGS[key])
+    cfg = CONFIGS[key]
+    return Llama(replace(cfg, qk_norm=True) if qk_norm else cfg)
 
 
 def param_count(cfg: LlamaConfig) -> int:
     hd = cfg.dim // cfg.n_heads
     attn = cfg.dim * hd * (cfg.n_heads * 2 + cfg.n_kv_heads * 2)
     ffn = 3 * cfg.dim * cfg.ffn_dim
-    return cfg.n_layers * (attn + ffn + 2 * cfg.dim) + 2 * cfg.vocab_size * cfg.dim + cfg.dim
+    qk = 2 * hd if cfg.qk_norm else 0
+    return cfg.n_layers * (attn + ffn + 2 * cfg.dim + qk) + 2 * cfg.vocab_size * cfg.dim + cfg.dim

@@ -41,6 +41,24 @@ def rope_ref(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Ten
     return out.view(x.shape).to(x.dtype)
 
 
+def qk_norm_rope_ref(q: torch.Tensor, k: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, cos: torch.Tensor,
+                     sin: torch.Tensor, eps: float = 1e-5):
+    """QK-norm fused with RoPE, in fp32: every head-row ``x`` of q [B, S, Hq, hd] and k [B, S, Hkv, hd] becomes
+    ``rope(x * rsqrt(mean(x^2) + eps) * w)`` with ``w = wq`` for q and ``wk`` for k (one [hd] gain shared by the
+    heads of a projection) and the pairing of ``rope_ref``; rounded to the input's dtype once. -> (q', k')"""
+    S = q.shape[1]
+    c, s = cos[:S].float()[None, :, None, :], sin[:S].float()[None, :, None, :]
+
+    def one(x, w):
+        xf = x.float()
+        n = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * w.float()
+        n = n.view(*x.shape[:-1], -1, 2)
+        n0, n1 = n[..., 0], n[..., 1]
+        return torch.stack([n0 * c - n1 * s, n0 * s + n1 * c], -1).view(x.shape).to(x.dtype)
+
+    return one(q, wq), one(k, wk)
+
+
 # ------------------------------------------------------------------ autograd functions
 def _aligned(t: torch.Tensor) -> torch.Tensor:
     """``t`` contiguous and 16-byte aligned, as the RMSNorm 4-wide and the cross-entropy kernels read
@@ -130,6 +148,32 @@ class _RoPE(torch.autograd.Function):
         return native.C().rope(gy.contiguous(), cos, sin, True), None, None
 
 
+class _QKNormRoPE(torch.autograd.Function):
+    """(q', k') in one launch; the backward recomputes the row statistics from the saved q and k (one launch
+    plus the fixed-order sum of the gain-gradient partials)."""
+
+    @staticmethod
+    def forward(ctx, q, k, wq, wk, cos, sin, eps):
+        ctx.set_materialize_grads(False)  # an unused output's gradient arrives as None, not as zeros
+        q, k, wq, wk = _aligned(q), _aligned(k), _aligned(wq), _aligned(wk)
+        cos, sin = _aligned(cos.float()), _aligned(sin.float())
+        yq, yk = native.C().qk_norm_rope_fwd(q, k, wq, wk, cos, sin, eps)
+        ctx.save_for_backward(q, k, wq, wk, cos, sin)
+        ctx.eps = eps
+        return yq, yk
+
+    @staticmethod
+    def backward(ctx, gq, gk):
+        if gq is None and gk is None:
+            return (None,) * 7
+        q, k, wq, wk, cos, sin = ctx.saved_tensors
+        # the kernel reads both gradients in the inputs' dtype; a missing one is zeros of that output only
+        gq = torch.zeros_like(q) if gq is None else _aligned(gq.to(q.dtype))
+        gk = torch.zeros_like(k) if gk is None else _aligned(gk.to(k.dtype))
+        grads = native.C().qk_norm_rope_bwd(q, k, wq, wk, cos, sin, gq, gk, ctx.eps)
+        return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[:4])) + (None,) * 3
+
+
 def _native_ok(*ts) -> bool:
     return all(t.is_cuda for t in ts) and all(t.dtype in (torch.float32, torch.bfloat16) for t in ts)
 
@@ -174,6 +218,31 @@ def rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor:
     if _native_ok(x):
         return _RoPE.apply(x, cos, sin)
     return rope_ref(x, cos, sin)
+
+
+def qk_norm_rope(q: torch.Tensor, k: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, cos: torch.Tensor,
+                 sin: torch.Tensor, eps: float = 1e-5):
+    """QK-norm fused with RoPE -> ``(q', k')``. ``q``: [B, S, Hq, hd], ``k``: [B, S, Hkv, hd]; every head-row
+    ``x`` at position ``s`` becomes ``rope(x * rsqrt(mean(x^2) + eps) * w, s)`` with the learned gain
+    ``w = wq`` ([hd], shared by the heads of q) or ``wk``, the tables ``cos`` / ``sin`` [>= S, hd/2] and the
+    pairing of ``rope``: the per-head norm of Qwen3 / Gemma 3 (not a norm over the whole projection),
+    computed in fp32 and rounded to the input's dtype once.
+
+    When every tensor is on the GPU, q and k share fp32 or bf16, hd is 64 or 128 and the gains are fp32,
+    one gfx950 launch does both projections forward and one (plus the fixed-order sum of the gain
+    gradients' partials, no atomics: the same bits every run) backward. Anything else (CPU, another head
+    size, bf16 gains, q and k of different dtypes) runs ``qk_norm_rope_ref``.
+
+    Saved for backward: the pre-norm ``q`` and ``k`` (the row statistics are recomputed from them). Plain
+    ``rope`` saves no activation, so QK-norm adds tokens x (Hq + Hkv) x hd saved elements per layer."""
+    ts = (q, k, wq, wk, cos, sin)
+    if (all(t.is_cuda for t in ts) and q.dim() == 4 and k.dim() == 4 and q.dtype == k.dtype
+            and q.dtype in (torch.float32, torch.bfloat16) and q.shape[-1] in (64, 128)
+            and q.shape[:2] == k.shape[:2] and q.shape[-1] == k.shape[-1] and q.shape[2] > 0 and k.shape[2] > 0
+            and wq.dtype == torch.float32 and wk.dtype == torch.float32
+            and wq.shape == q.shape[-1:] and wk.shape == q.shape[-1:]):
+        return _QKNormRoPE.apply(q, k, wq, wk, cos, sin, float(eps))
+    return qk_norm_rope_ref(q, k, wq, wk, cos, sin, eps)
 
 
 # ------------------------------------------------------------------ bf16 projections with fp32 masters

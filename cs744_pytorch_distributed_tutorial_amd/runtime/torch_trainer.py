@@ -38,16 +38,18 @@ from ..parallel import DistributedDataParallel, make_comm, make_sync
 from ..utils.metrics import roctx_range
 
 
-def build_model(name: str) -> nn.Module:
+def build_model(name: str, qk_norm: bool = False) -> nn.Module:
     from ..models import resnet, vgg
     n = name.lower().replace("-", "")
+    if qk_norm and not (n.startswith("llama") or n.startswith("decoder")):
+        raise ValueError(f"qk_norm (the per-head RMSNorm of q and k) is for the LM models, not {name!r}")
     if n.startswith("vgg"):
         return vgg.VGG(n.upper())
     if n in ("resnet18", "resnet34", "resnet50", "resnet101"):
         return getattr(resnet, n)(layout=os.environ.get("CS744_RESNET_LAYOUT", "nhwc"))
     if n.startswith("llama") or n.startswith("decoder"):
         from ..models import llama
-        return llama.build(name.lower())
+        return llama.build(name.lower(), qk_norm=qk_norm)
     raise ValueError(f"unknown model {name!r}")
 
 
@@ -104,7 +106,7 @@ class TorchTrainer:
                  seq_len: int = 0, fused_sgd: bool = True, optimizer: Optional[str] = None, betas=(0.9, 0.95),
                  eps: float = 1e-8, max_grad_norm: Optional[float] = None, doc_len: Optional[int] = None,
                  loss_mask: Optional[str] = None, z_loss: Optional[float] = None, fused_head: Optional[bool] = None,
-                 fused_residual: Optional[bool] = None):
+                 fused_residual: Optional[bool] = None, qk_norm: Optional[bool] = None):
         """``doc_len``: pack documents of about that many tokens into every row of the synthetic token
         pool (``SyntheticBatches``) and train with document-masked attention: ``step()`` derives the
         document of every token from the EOS tokens of its input, the way real packed data would be
@@ -130,6 +132,11 @@ class TorchTrainer:
         traffic on the residual stream. ``None`` takes ``CS744_FUSED_RESIDUAL=1`` if set, else off. LM
         models only.
 
+        ``qk_norm``: build the decoder with QK-norm (``LlamaConfig.qk_norm``): a per-head RMSNorm of q and
+        k with a learned [head_dim] gain each, fused with RoPE (``ops.lm.qk_norm_rope``). It adds the
+        parameters ``attention.q_norm.weight`` / ``k_norm.weight`` to every layer (1-D: no weight decay
+        under AdamW). ``None`` takes ``CS744_QK_NORM=1`` if set, else off. LM models only.
+
         ``optimizer``: ``"sgd"`` (momentum SGD, the default) or ``"adamw"`` (AdamW with decoupled weight
         decay on the parameters with ``dim() >= 2`` only, and global-norm gradient clipping at
         ``max_grad_norm`` when that is set). ``None`` takes ``CS744_OPTIMIZER`` if set, else ``"sgd"``;
@@ -146,7 +153,10 @@ class TorchTrainer:
             torch.backends.cudnn.benchmark = True
         self.device, self.world, self.B = device, world, batch_size
         self.model_name = model
-        self.module = build_model(model).to(device)
+        if qk_norm is None:
+            qk_norm = os.environ.get("CS744_QK_NORM", "0") == "1"
+        self.qk_norm = bool(qk_norm)
+        self.module = build_model(model, qk_norm=self.qk_norm).to(device)
         self.is_lm = hasattr(self.module, "vocab_size")
         self.channels_last = not self.is_lm and os.environ.get("CS744_CHANNELS_LAST", "0") == "1"
         if self.channels_last:

@@ -314,6 +314,77 @@ torch::Tensor rope(torch::Tensor x, torch::Tensor cosv, torch::Tensor sinv, bool
   return out;
 }
 
+// the host checks shared by qk_norm_rope_fwd / _bwd
+void qk_check(const torch::Tensor& q, const torch::Tensor& k, const torch::Tensor& wq, const torch::Tensor& wk,
+              const torch::Tensor& cosv, const torch::Tensor& sinv) {
+  check(q, "q"); check(k, "k"); check(wq, "wq"); check(wk, "wk"); check(cosv, "cos"); check(sinv, "sin");
+  for (auto* t : {&k, &wq, &wk, &cosv, &sinv})
+    TORCH_CHECK(t->device() == q.device(), "qk_norm_rope: all tensors must be on one device");
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4, "qk_norm_rope: q and k must be [B, S, H, head_dim]");
+  TORCH_CHECK(q.size(0) == k.size(0) && q.size(1) == k.size(1) && q.size(3) == k.size(3),
+              "qk_norm_rope: q and k must agree in B, S and head_dim");
+  TORCH_CHECK(q.scalar_type() == k.scalar_type(), "qk_norm_rope: q and k must have one dtype");
+  TORCH_CHECK(q.scalar_type() == at::kFloat || q.scalar_type() == at::kBFloat16,
+              "qk_norm_rope: q and k must be float32 or bfloat16");
+  const int64_t S = q.size(1), hd = q.size(3);
+  TORCH_CHECK(hd == 64 || hd == 128, "qk_norm_rope: head_dim must be 64 or 128, got ", hd);
+  TORCH_CHECK(q.size(2) > 0 && k.size(2) > 0, "qk_norm_rope: q and k need at least one head");
+  for (auto* w : {&wq, &wk})
+    TORCH_CHECK(w->scalar_type() == at::kFloat && w->dim() == 1 && w->size(0) == hd,
+                "qk_norm_rope: the gains must be fp32 [head_dim]");
+  for (auto* t : {&cosv, &sinv})
+    TORCH_CHECK(t->scalar_type() == at::kFloat && t->dim() == 2 && t->size(0) >= S && t->size(1) == hd / 2,
+                "qk_norm_rope: cos / sin must be fp32 [>= S, head_dim / 2]");
+  TORCH_CHECK(q.size(0) * S * (q.size(2) + k.size(2)) <= INT_MAX, "qk_norm_rope: too many head-rows");
+  check_aligned(q, "q"); check_aligned(k, "k"); check_aligned(wq, "wq"); check_aligned(wk, "wk");
+  check_aligned(cosv, "cos"); check_aligned(sinv, "sin");
+}
+
+// q [B, S, Hq, hd], k [B, S, Hkv, hd] -> {q', k'}: per-head RMSNorm with the gains wq / wk, then RoPE
+std::vector<torch::Tensor> qk_norm_rope_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor wq, torch::Tensor wk,
+                                            torch::Tensor cosv, torch::Tensor sinv, double eps) {
+  qk_check(q, k, wq, wk, cosv, sinv);
+  DevGuard g(q.device());
+  auto yq = torch::empty_like(q), yk = torch::empty_like(k);
+  if (q.size(0) * q.size(1) == 0) return {yq, yk};  // no rows: no launch
+  check_aligned(yq, "q'"); check_aligned(yk, "k'");
+  CS_LAUNCH(cs_qk_norm_rope_fwd(dt_of(q), q.data_ptr(), k.data_ptr(), wq.data_ptr<float>(), wk.data_ptr<float>(),
+                                cosv.data_ptr<float>(), sinv.data_ptr<float>(), yq.data_ptr(), yk.data_ptr(),
+                                (int)q.size(0), (int)q.size(1), (int)q.size(2), (int)k.size(2), (int)q.size(3),
+                                (float)eps, cur_stream()));
+  return {yq, yk};
+}
+
+// the saved inputs and the gradients of q', k' -> {dq, dk, dwq, dwk}; dwq and dwk are the halves of one buffer
+std::vector<torch::Tensor> qk_norm_rope_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor wq, torch::Tensor wk,
+                                            torch::Tensor cosv, torch::Tensor sinv, torch::Tensor gq, torch::Tensor gk,
+                                            double eps) {
+  qk_check(q, k, wq, wk, cosv, sinv);
+  check(gq, "gq"); check(gk, "gk");
+  TORCH_CHECK(gq.device() == q.device() && gk.device() == q.device(),
+              "qk_norm_rope: all tensors must be on one device");
+  TORCH_CHECK(gq.sizes() == q.sizes() && gq.scalar_type() == q.scalar_type() && gk.sizes() == k.sizes() &&
+                  gk.scalar_type() == k.scalar_type(),
+              "qk_norm_rope_bwd: the gradients must match q and k in shape and dtype");
+  check_aligned(gq, "gq"); check_aligned(gk, "gk");
+  DevGuard g(q.device());
+  const int64_t hd = q.size(3), rows = q.size(0) * q.size(1) * (q.size(2) + k.size(2));
+  auto dq = torch::empty_like(q), dk = torch::empty_like(k);
+  if (rows == 0) {  // no rows: the weight gradients are the empty sum, no launch
+    auto dw = torch::zeros({2 * hd}, wq.options());
+    return {dq, dk, dw.slice(0, 0, hd), dw.slice(0, hd, 2 * hd)};
+  }
+  auto dw = torch::empty({2 * hd}, wq.options());
+  auto part = torch::empty({(int64_t)cs_qk_norm_rope_partials(rows, (int)hd), 2 * hd}, wq.options());
+  check_aligned(dq, "dq"); check_aligned(dk, "dk"); check_aligned(dw, "dw"); check_aligned(part, "part");
+  CS_LAUNCH(cs_qk_norm_rope_bwd(dt_of(q), q.data_ptr(), k.data_ptr(), wq.data_ptr<float>(), wk.data_ptr<float>(),
+                                cosv.data_ptr<float>(), sinv.data_ptr<float>(), gq.data_ptr(), gk.data_ptr(),
+                                dq.data_ptr(), dk.data_ptr(), dw.data_ptr<float>(), part.data_ptr<float>(),
+                                (int)q.size(0), (int)q.size(1), (int)q.size(2), (int)k.size(2), (int)hd, (float)eps,
+                                cur_stream()));
+  return {dq, dk, dw.slice(0, 0, hd), dw.slice(0, hd, 2 * hd)};
+}
+
 // q [B, S, Hq, D], k/v [B, S, Hkv, D] bf16 contiguous -> {o [B, S, Hq, D], lse f32 [B, Hq, S]}
 void attn_check(const torch::Tensor& q, const torch::Tensor& k, const torch::Tensor& v) {
   for (auto* t : {&q, &k, &v}) {
@@ -494,6 +565,16 @@ void register_lm_ops(pybind11::module& m) {
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("rope", &rope);
   namespace py = pybind11;
+  m.def("qk_norm_rope_fwd", &qk_norm_rope_fwd,
+        "per-head RMSNorm of q [B,S,Hq,hd] and k [B,S,Hkv,hd] (fp32 gains [hd]) fused with RoPE -> (q', k')",
+        py::arg("q"), py::arg("k"), py::arg("wq"), py::arg("wk"), py::arg("cos"), py::arg("sin"),
+        py::arg("eps") = 1e-5);
+  m.def("qk_norm_rope_bwd", &qk_norm_rope_bwd, "its backward from the saved inputs -> (dq, dk, dwq, dwk)",
+        py::arg("q"), py::arg("k"), py::arg("wq"), py::arg("wk"), py::arg("cos"), py::arg("sin"), py::arg("gq"),
+        py::arg("gk"), py::arg("eps") = 1e-5);
+  m.def("qk_norm_rope_rows_per_block", [](int64_t hd) { return cs_qk_norm_rope_rows_per_block((int)hd); },
+        "head-rows a block of the QK-norm kernels holds at a time (0: unsupported head_dim)");
+  m.def("qk_norm_rope_max_blocks", &cs_qk_norm_rope_max_blocks, "the grid cap of the QK-norm kernels");
   m.def("attn_fwd", &attn_fwd, "flash attention forward (bf16 [B,S,H,D], GQA, causal; kstart / qend: document mask)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"), py::arg("causal"),
         py::arg("kstart") = c10::nullopt, py::arg("qend") = c10::nullopt);

@@ -450,6 +450,24 @@ hipError_t cs_gemm_bf16(int a_kmajor, const void* A, int64_t lda, int b_kmajor, 
                         int64_t ldc, int M, int N, int K, int out_mode, int splits, int64_t slab, hipStream_t stream);
 hipError_t cs_rope(int dt, const void* x, const float* cosv, const float* sinv, void* out, int B, int S, int H, int hd,
                    int inverse, hipStream_t s);
+// QK-norm fused with RoPE: per head-row of q [B, S, Hq, hd] and k [B, S, Hkv, hd] (one dtype dt, hd 64 or
+// 128), y = rope(x * rsqrt(mean(x^2) + eps) * w) with the fp32 gain wq / wk [hd] and the fp32 tables
+// cos / sin [>= S, hd / 2], rounded once; one launch for both projections. hipErrorInvalidValue on another
+// hd or dtype, on B * S * (Hq + Hkv) > INT_MAX, and on a null or not 16-byte aligned pointer.
+hipError_t cs_qk_norm_rope_fwd(int dt, const void* q, const void* k, const float* wq, const float* wk,
+                               const float* cosv, const float* sinv, void* yq, void* yk, int B, int S, int Hq, int Hkv,
+                               int hd, float eps, hipStream_t s);
+// its backward from the saved inputs (the row statistics are recomputed): dq, dk in dt and dw = [dwq | dwk]
+// (2 * hd floats), summed in a fixed order from part, [cs_qk_norm_rope_partials(rows, hd)][2 * hd] floats of
+// scratch with rows = B * S * (Hq + Hkv): two launches, no atomics
+hipError_t cs_qk_norm_rope_bwd(int dt, const void* q, const void* k, const float* wq, const float* wk,
+                               const float* cosv, const float* sinv, const void* gq, const void* gk, void* dq,
+                               void* dk, float* dw, float* part, int B, int S, int Hq, int Hkv, int hd, float eps,
+                               hipStream_t s);
+// head-rows a block holds at a time (0: unsupported hd), the grid cap, and the blocks (= partial rows) of a launch
+int cs_qk_norm_rope_rows_per_block(int hd);
+int cs_qk_norm_rope_max_blocks();
+int cs_qk_norm_rope_partials(int64_t rows, int hd);
 // channels-last (NHWC) CNN kernels (cnn_nhwc.hip), fp32 / bf16 activations, M = B*H*W rows of C.
 // BatchNorm: stat / coef / part exactly as the NCHW kernels above (part: cs_bn_nhwc_partials floats).
 // mask (optional, M*C/V bytes, V = cs_bn_nhwc_vec): the forward writes each V-channel vector's

@@ -490,6 +490,124 @@ int grid_for(size_t n) {
   return (int)(b > 16384 ? 16384 : (b == 0 ? 1 : b));
 }
 
+// ---- QK-norm: RMSNorm over the head dimension of q [B, S, Hq, HD] and k [B, S, Hkv, HD] (one fp32 gain
+// [HD] per projection) followed by the rotation of rope_kernel, rounded once. One launch walks the
+// nq = B*S*Hq head-rows of q and then the nk = B*S*Hkv of k as one row range [0, nq + nk).
+// A head-row lives in HD / 4 adjacent lanes of one wave (half a wave for HD = 128, a quarter for
+// HD = 64), 4 elements = 2 rotation pairs per lane: 8-byte (bf16) / 16-byte (fp32) accesses, the row
+// sums by __shfl_xor inside those lanes, the rotation inside a lane. A block holds kQKThreads / (HD / 4)
+// rows at a time and walks the range with the grid's stride; the grid is capped at kQKMaxBlocks.
+// The shuffles run in uniform control flow: rows past the end load zeros and store nothing.
+constexpr int kQKThreads = 256, kQKMaxBlocks = 2048;
+
+template <int HD>
+struct QKRow {
+  static constexpr int kLanes = HD / 4, kRows = kQKThreads / kLanes;
+  bool live, isq;
+  size_t off;   // element offset of this lane's 4 elements inside its own projection
+  size_t trig;  // offset of this lane's 2 (cos, sin) entries
+  __device__ __forceinline__ QKRow(int64_t row, int lane, int nq, int nk, int S, int Hq, int Hkv) {
+    live = row < (int64_t)nq + nk;
+    isq = row < nq;
+    const int lr = live ? (int)(isq ? row : row - nq) : 0;
+    const int s = (lr / (isq ? Hq : Hkv)) % S;  // the projection's own head count
+    off = (size_t)lr * HD + 4 * lane;
+    trig = (size_t)s * (HD / 2) + 2 * lane;
+  }
+};
+
+template <int LANES>
+__device__ __forceinline__ float qk_row_sum(float v) {
+#pragma unroll
+  for (int o = LANES / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+template <typename T, int HD>
+__global__ __launch_bounds__(kQKThreads) void qk_norm_rope_fwd_kernel(
+    const T* __restrict__ q, const T* __restrict__ k, const float* __restrict__ wq, const float* __restrict__ wk,
+    const float* __restrict__ cosv, const float* __restrict__ sinv, T* __restrict__ yq, T* __restrict__ yk, int nq,
+    int nk, int S, int Hq, int Hkv, float eps) {
+  using R = QKRow<HD>;
+  const int lane = threadIdx.x % R::kLanes, slot = threadIdx.x / R::kLanes;
+  const float4 wqv = ld4(wq + 4 * lane), wkv = ld4(wk + 4 * lane);
+  const int64_t total = (int64_t)nq + nk;
+  for (int64_t base = (int64_t)blockIdx.x * R::kRows; base < total; base += (int64_t)gridDim.x * R::kRows) {
+    const R row(base + slot, lane, nq, nk, S, Hq, Hkv);
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (row.live) v = ld4((row.isq ? q : k) + row.off);
+    const float r = rms_rstd(qk_row_sum<R::kLanes>(rms_ss4(v)), HD, eps);
+    if (row.live) {
+      const float2 c = *reinterpret_cast<const float2*>(cosv + row.trig);
+      const float2 sn = *reinterpret_cast<const float2*>(sinv + row.trig);
+      const float4 n = rms_scale4(v, r, row.isq ? wqv : wkv);
+      st4((row.isq ? yq : yk) + row.off, make_float4(n.x * c.x - n.y * sn.x, n.x * sn.x + n.y * c.x,
+                                                     n.z * c.y - n.w * sn.y, n.z * sn.y + n.w * c.y));
+    }
+  }
+}
+
+// gn = R^T g (the rotation with -sin), xh = x r, c = mean(w gn xh), dx = r (w gn - xh c), and the row's
+// weight-gradient term t = gn xh; r is recomputed from x. A thread adds the t of its rows, in row
+// order, into one q and one k accumulator for its 4 columns; the block's row slots are then added in
+// slot order through LDS and the block stores one partial row [q sums | k sums] of 2 * HD floats
+// (zeros where it had no row of that kind). colsum4_kernel over the partials gives [dwq | dwk]: no
+// atomics, the same bits every run.
+template <typename T, int HD>
+__global__ __launch_bounds__(kQKThreads) void qk_norm_rope_bwd_kernel(
+    const T* __restrict__ q, const T* __restrict__ k, const float* __restrict__ wq, const float* __restrict__ wk,
+    const float* __restrict__ cosv, const float* __restrict__ sinv, const T* __restrict__ gq,
+    const T* __restrict__ gk, T* __restrict__ dq, T* __restrict__ dk, float* __restrict__ part, int nq, int nk, int S,
+    int Hq, int Hkv, float eps) {
+  using R = QKRow<HD>;
+  __shared__ float4 sh[2][R::kRows][R::kLanes];
+  const int lane = threadIdx.x % R::kLanes, slot = threadIdx.x / R::kLanes;
+  const float4 wqv = ld4(wq + 4 * lane), wkv = ld4(wk + 4 * lane);
+  float4 aq = make_float4(0.f, 0.f, 0.f, 0.f), ak = aq;
+  const int64_t total = (int64_t)nq + nk;
+  for (int64_t base = (int64_t)blockIdx.x * R::kRows; base < total; base += (int64_t)gridDim.x * R::kRows) {
+    const R row(base + slot, lane, nq, nk, S, Hq, Hkv);
+    float4 x = make_float4(0.f, 0.f, 0.f, 0.f), gn = x;
+    const float4 w = row.isq ? wqv : wkv;
+    if (row.live) {
+      x = ld4((row.isq ? q : k) + row.off);
+      const float4 g = ld4((row.isq ? gq : gk) + row.off);
+      const float2 c = *reinterpret_cast<const float2*>(cosv + row.trig);
+      const float2 sn = *reinterpret_cast<const float2*>(sinv + row.trig);
+      gn = make_float4(g.x * c.x + g.y * sn.x, g.y * c.x - g.x * sn.x, g.z * c.y + g.w * sn.y,
+                       g.w * c.y - g.z * sn.y);
+    }
+    const float ss = qk_row_sum<R::kLanes>(rms_ss4(x));
+    const float dot = qk_row_sum<R::kLanes>(rms_dot4(w, gn, x));
+    if (row.live) {
+      const float r = rms_rstd(ss, HD, eps);
+      const float4 xh = make_float4(x.x * r, x.y * r, x.z * r, x.w * r);
+      const float c = r * dot / (float)HD;  // mean(w gn xh)
+      st4((row.isq ? dq : dk) + row.off,
+          make_float4(r * (w.x * gn.x - xh.x * c), r * (w.y * gn.y - xh.y * c), r * (w.z * gn.z - xh.z * c),
+                      r * (w.w * gn.w - xh.w * c)));
+      const float4 t = make_float4(gn.x * xh.x, gn.y * xh.y, gn.z * xh.z, gn.w * xh.w);
+      if (row.isq) {  // a row adds to its own projection's sums only
+        aq.x += t.x; aq.y += t.y; aq.z += t.z; aq.w += t.w;
+      } else {
+        ak.x += t.x; ak.y += t.y; ak.z += t.z; ak.w += t.w;
+      }
+    }
+  }
+  sh[0][slot][lane] = aq;
+  sh[1][slot][lane] = ak;
+  __syncthreads();
+  if (threadIdx.x >= 2 * R::kLanes) return;
+  // threads [0, kLanes): the q columns, [kLanes, 2 kLanes): the k columns; slots in order
+  const int which = threadIdx.x / R::kLanes;
+  float4 t = sh[which][0][lane];
+  for (int l = 1; l < R::kRows; ++l) {
+    const float4 u = sh[which][l][lane];
+    t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w;
+  }
+  st4(part + (size_t)blockIdx.x * (2 * HD) + which * HD + 4 * lane, t);
+}
+
 // ---- softmax cross-entropy over bf16 / fp32 logits [R, V] (V % 8 == 0), mean over rows:
 // forward = one read of the logits (online max / sum-exp per row: 8-element vectors, wave
 // shuffles, then the 4 waves in order) -> per-row loss and log-sum-exp; backward = one more read
@@ -1031,5 +1149,73 @@ hipError_t cs_rope(int dt, const void* x, const float* cosv, const float* sinv, 
   if (npairs == 0) return hipSuccess;
   CS_DT_DISPATCH(dt, hipLaunchKernelGGL((rope_kernel<T>), dim3(grid_for(npairs)), dim3(256), 0, s, (const T*)x, cosv,
                                         sinv, (T*)out, S, H, hd, npairs, inverse ? -1.f : 1.f));
+  return hipGetLastError();
+}
+
+int cs_qk_norm_rope_rows_per_block(int hd) { return hd == 64 || hd == 128 ? kQKThreads / (hd / 4) : 0; }
+
+int cs_qk_norm_rope_max_blocks() { return kQKMaxBlocks; }
+
+int cs_qk_norm_rope_partials(int64_t rows, int hd) {
+  const int rpb = cs_qk_norm_rope_rows_per_block(hd);
+  if (rpb == 0 || rows <= 0) return 0;
+  const int64_t b = (rows + rpb - 1) / rpb;
+  return (int)(b > kQKMaxBlocks ? kQKMaxBlocks : b);
+}
+
+namespace {
+
+// the host-side range checks of both launchers; rows = B * S * (Hq + Hkv) must fit an int
+bool qk_args_ok(int dt, int B, int S, int Hq, int Hkv, int hd) {
+  if (dt != CS_F32 && dt != CS_BF16) return false;
+  if (hd != 64 && hd != 128) return false;
+  if (B <= 0 || S <= 0 || Hq <= 0 || Hkv <= 0) return false;
+  return (int64_t)B * S * ((int64_t)Hq + Hkv) <= 0x7fffffff;
+}
+
+bool qk_ptrs_ok(std::initializer_list<const void*> ps) {
+  for (const void* p : ps)
+    if (p == nullptr) return false;
+  return aligned16(ps);
+}
+
+}  // namespace
+
+#define CS_QK_DISPATCH(dt, hd, ...)                                     \
+  CS_DT_DISPATCH(dt, if ((hd) == 64) {                                  \
+    constexpr int HD = 64;                                              \
+    __VA_ARGS__;                                                        \
+  } else {                                                              \
+    constexpr int HD = 128;                                             \
+    __VA_ARGS__;                                                        \
+  })
+
+hipError_t cs_qk_norm_rope_fwd(int dt, const void* q, const void* k, const float* wq, const float* wk,
+                               const float* cosv, const float* sinv, void* yq, void* yk, int B, int S, int Hq, int Hkv,
+                               int hd, float eps, hipStream_t s) {
+  if (B == 0 || S == 0) return hipSuccess;
+  if (!qk_args_ok(dt, B, S, Hq, Hkv, hd) || !qk_ptrs_ok({q, k, wq, wk, cosv, sinv, yq, yk}))
+    return hipErrorInvalidValue;
+  const int nq = B * S * Hq, nk = B * S * Hkv;
+  const int grid = cs_qk_norm_rope_partials((int64_t)nq + nk, hd);
+  CS_QK_DISPATCH(dt, hd, hipLaunchKernelGGL((qk_norm_rope_fwd_kernel<T, HD>), dim3(grid), dim3(kQKThreads), 0, s,
+                                            (const T*)q, (const T*)k, wq, wk, cosv, sinv, (T*)yq, (T*)yk, nq, nk, S,
+                                            Hq, Hkv, eps));
+  return hipGetLastError();
+}
+
+hipError_t cs_qk_norm_rope_bwd(int dt, const void* q, const void* k, const float* wq, const float* wk,
+                               const float* cosv, const float* sinv, const void* gq, const void* gk, void* dq,
+                               void* dk, float* dw, float* part, int B, int S, int Hq, int Hkv, int hd, float eps,
+                               hipStream_t s) {
+  if (B == 0 || S == 0) return hipSuccess;
+  if (!qk_args_ok(dt, B, S, Hq, Hkv, hd) || !qk_ptrs_ok({q, k, wq, wk, cosv, sinv, gq, gk, dq, dk, dw, part}))
+    return hipErrorInvalidValue;
+  const int nq = B * S * Hq, nk = B * S * Hkv;
+  const int P = cs_qk_norm_rope_partials((int64_t)nq + nk, hd);
+  CS_QK_DISPATCH(dt, hd, hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<T, HD>), dim3(P), dim3(kQKThreads), 0, s,
+                                            (const T*)q, (const T*)k, wq, wk, cosv, sinv, (const T*)gq, (const T*)gk,
+                                            (T*)dq, (T*)dk, part, nq, nk, S, Hq, Hkv, eps));
+  hipLaunchKernelGGL((colsum4_kernel<float>), dim3((2 * hd / 4 + 15) / 16), dim3(256), 0, s, part, P, 2 * hd, dw);
   return hipGetLastError();
 }
