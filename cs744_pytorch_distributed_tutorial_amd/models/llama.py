@@ -18,6 +18,9 @@ rewrites (``ops.lm.ShadowLinear``): no per-step weight casts, fp32 weight gradie
 of the GEMM. With ``LlamaConfig.qk_norm`` (opt-in) q and k get a per-head RMSNorm fused with their RoPE
 (``ops.lm.qk_norm_rope``). With ``Llama.fused_residual`` (opt-in) every residual add after the first norm runs
 inside the RMSNorm that follows it (``ops.lm.add_rms_norm``).
+
+Inference: ``Llama.generate`` = ``prefill`` (the training blocks, k and v copied into an ``ops.attention.KVCache``)
+plus one ``decode_step`` per token (split-KV decode attention, ``ops.attention.decode_attention``; docs/decode_attention.md).
 """
 from __future__ import annotations
 
@@ -100,8 +103,9 @@ class Attention(nn.Module):
             self.q_norm = RMSNorm(self.hd, cfg.norm_eps)
             self.k_norm = RMSNorm(self.hd, cfg.norm_eps)
 
-    def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, doc=None) -> torch.Tensor:
-        """``doc``: ``ops.attention.DocBounds`` of a packed batch (attention stays inside a document)."""
+    def _qkv(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> tuple:
+        """The projections of ``x`` [B, S, dim] as [B, S, H, hd], q and k after (QK-norm and) RoPE with the
+        table rows ``cos`` / ``sin`` [S, hd/2]: row s of the tables belongs to position s of the S axis."""
         B, S, _ = x.shape
         q = self.wq(x).view(B, S, self.nh, self.hd)
         k = self.wk(x).view(B, S, self.nkv, self.hd)
@@ -110,6 +114,17 @@ class Attention(nn.Module):
             q, k = _ops().qk_norm_rope(q, k, self.q_norm.weight, self.k_norm.weight, cos, sin, self.q_norm.eps)
         else:
             q, k = _ops().rope(q, cos, sin), _ops().rope(k, cos, sin)
+        return q, k, v
+
+    def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, doc=None, kv_out=None) -> torch.Tensor:
+        """``doc``: ``ops.attention.DocBounds`` of a packed batch (attention stays inside a document).
+        ``kv_out``: a pair of cache tensors [B, Smax >= S, Hkv, hd] (``Llama.prefill``); the post-RoPE k and v
+        are copied into their first S positions."""
+        B, S, _ = x.shape
+        q, k, v = self._qkv(x, cos, sin)
+        if kv_out is not None:
+            kv_out[0][:, :S].copy_(k)
+            kv_out[1][:, :S].copy_(v)
         from ..ops.attention import attention, attention_ref, native_ok
         if native_ok(q, k, v):
             o = attention(q, k, v, causal=True, doc=doc)  # [B, S, Hq, hd], gfx950 flash attention
@@ -119,6 +134,22 @@ class Attention(nn.Module):
             q, k, v = q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2)
             o = F.scaled_dot_product_attention(q, k, v, is_causal=True, enable_gqa=self.nkv != self.nh).transpose(1, 2)
         return self.wo(o.reshape(B, S, self.nh * self.hd))
+
+    def decode(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor,
+               slot: torch.Tensor, lens: torch.Tensor, bound: int) -> torch.Tensor:
+        """One new token per row against the cache. ``x``: [B, 1, dim]; ``cos`` / ``sin``: [B, hd/2], the table
+        rows of every row's own position; ``kc`` / ``vc``: this layer's caches [B, Smax, Hkv, hd]; ``slot``:
+        int64 [B], ``b * Smax + position`` where the new k and v rows go; ``lens``: int32 [B], the lengths
+        with the new token counted; ``bound``: a host-known upper bound of ``lens``."""
+        B = x.shape[0]
+        # [B, 1, H, hd] read as [1, B, H, hd]: the batch stands in the sequence axis of the RoPE ops, so
+        # row b is rotated by table row b
+        q, k, v = self._qkv(x.reshape(1, B, -1), cos, sin)
+        kc.view(-1, self.nkv, self.hd).index_copy_(0, slot, k.view(B, self.nkv, self.hd).to(kc.dtype))
+        vc.view(-1, self.nkv, self.hd).index_copy_(0, slot, v.view(B, self.nkv, self.hd).to(vc.dtype))
+        from ..ops.attention import decode_attention
+        o = decode_attention(q.view(B, self.nh, self.hd), kc[:, :bound], vc[:, :bound], lens)
+        return self.wo(o.reshape(B, 1, self.nh * self.hd))
 
 
 class FeedForward(nn.Module):
@@ -223,6 +254,118 @@ class Llama(nn.Module):
             for blk in self.layers:
                 h = blk(h, cos, sin, doc)
         return self.norm(h)
+
+    # ------------------------------------------------------------------ inference with a KV cache
+    def cache_dtype(self, device) -> torch.dtype:
+        """The dtype the projections come out in on ``device``: the autocast dtype under GPU autocast,
+        the parameters' dtype otherwise."""
+        if torch.device(device).type == "cuda" and torch.is_autocast_enabled("cuda"):
+            return torch.get_autocast_dtype("cuda")
+        return self.tok_embeddings.weight.dtype
+
+    @torch.no_grad()
+    def prefill(self, tokens: torch.Tensor, cache, prompt_lens=None, doc_ids=None) -> torch.Tensor:
+        """Run the prompt through the model and fill ``cache`` (``ops.attention.KVCache``): the logits
+        [B, V] of each row's last prompt token. ``tokens``: [B, S], right-padded; ``prompt_lens``: int [B],
+        every value in [1, S] (default: all S). The blocks run with causal flash attention, which already
+        keeps the padding out of the real positions; each layer's post-RoPE k and v go to ``cache[:, :S]``,
+        ``cache.lens`` becomes ``prompt_lens``, and the final norm and the head run on the B last rows only.
+        Packed documents (``doc_ids``) have no cached form and are refused."""
+        if doc_ids is not None:
+            raise ValueError("prefill: a document mask (doc_ids) cannot be combined with a KV cache")
+        if tokens.dim() != 2:
+            raise ValueError("prefill: tokens must be [B, S]")
+        B, S = tokens.shape
+        if cache.k.shape[0] != len(self.layers) or cache.k.shape[1] != B or cache.k.shape[2] < S or S < 1:
+            raise ValueError(f"prefill: the cache {tuple(cache.k.shape)} does not hold {len(self.layers)} layers of "
+                             f"[{B}, {S}] tokens")
+        dev = tokens.device
+        if prompt_lens is None:
+            lens = torch.full((B,), S, dtype=torch.int32, device=dev)
+        else:
+            lens = torch.as_tensor(prompt_lens).to(device=dev, dtype=torch.int32).reshape(B).clamp(0, S)
+        self._tables(cache.k.shape[2], dev)  # once, at the cache's length: decode_step gathers from them
+        cos, sin = self._tables(S, dev)
+        h = self.tok_embeddings(tokens)
+        for l, blk in enumerate(self.layers):
+            h = h + blk.attention(blk.attention_norm(h), cos, sin, kv_out=(cache.k[l], cache.v[l]))
+            h = h + blk.feed_forward(blk.ffn_norm(h))
+        last = (lens.long() - 1).clamp(min=0)
+        h = h[torch.arange(B, device=dev), last].unsqueeze(1)  # [B, 1, dim], gathered on the device
+        cache.lens, cache.bound = lens, S
+        return self.output(self.norm(h)).squeeze(1)
+
+    @torch.no_grad()
+    def decode_step(self, tok: torch.Tensor, cache) -> torch.Tensor:
+        """Append one token per row and return the logits [B, V] of the next one. Row b's position is
+        ``cache.lens[b]``, so rows may differ; every row must still have room (``lens[b] < Smax``: a full
+        row's write is clamped onto its last position). Nothing is read back from the device: the RoPE
+        table rows are gathered by position, the new k and v rows are scattered by a device index, and the
+        attention runs over ``cache[:, :bound]`` with ``bound`` the host-known prompt length plus steps."""
+        B = tok.shape[0]
+        Smax = cache.k.shape[2]
+        if cache.bound >= Smax:
+            raise ValueError(f"decode_step: the cache of {Smax} positions is full")
+        dev = tok.device
+        cos, sin = self._tables(Smax, dev)
+        pos = cache.lens.long().clamp(max=Smax - 1)
+        cos, sin = cos[pos], sin[pos]
+        slot = torch.arange(B, device=dev) * Smax + pos
+        lens = (pos + 1).int()
+        bound = cache.bound + 1
+        h = self.tok_embeddings(tok.view(B, 1))
+        for l, blk in enumerate(self.layers):
+            h = h + blk.attention.decode(blk.attention_norm(h), cos, sin, cache.k[l], cache.v[l], slot, lens, bound)
+            h = h + blk.feed_forward(blk.ffn_norm(h))
+        cache.lens, cache.bound = lens, bound
+        return self.output(self.norm(h)).squeeze(1)
+
+    @torch.no_grad()
+    def generate(self, tokens: torch.Tensor, max_new_tokens: int, prompt_lens=None, temperature: float = 0.0,
+                 top_k=None, eos_id=None, generator=None) -> torch.Tensor:
+        """``int64 [B, max_new_tokens]``: the continuation of every row of ``tokens`` [B, S] (right-padded,
+        ``prompt_lens`` int [B]), one ``prefill`` and then one ``decode_step`` per token. ``temperature == 0``
+        is greedy argmax; otherwise a token is drawn (``torch.multinomial`` with ``generator``) from
+        ``softmax(logits / temperature)``, restricted to the ``top_k`` largest logits when given. A row that
+        has emitted ``eos_id`` keeps emitting it (a device-side mask: no early exit, no synchronisation)."""
+        from ..ops.attention import KVCache
+        B, S = tokens.shape
+        if max_new_tokens < 0 or S + max_new_tokens > self.cfg.max_seq:
+            raise ValueError(f"generate: {S} prompt + {max_new_tokens} new tokens exceed max_seq {self.cfg.max_seq}")
+        if temperature < 0 or (top_k is not None and top_k < 1):
+            raise ValueError("generate: temperature must be >= 0 and top_k >= 1")
+        dev = tokens.device
+        if max_new_tokens == 0:
+            return torch.empty(B, 0, dtype=torch.int64, device=dev)
+        cache = KVCache.allocate(self.cfg, B, S + max_new_tokens, dev, self.cache_dtype(dev))
+        logits = self.prefill(tokens, cache, prompt_lens)
+        return self.decode_loop(logits, cache, max_new_tokens, temperature, top_k, eos_id, generator)
+
+    @torch.no_grad()
+    def decode_loop(self, logits: torch.Tensor, cache, max_new_tokens: int, temperature: float = 0.0, top_k=None,
+                    eos_id=None, generator=None) -> torch.Tensor:
+        """The token loop of ``generate`` from the logits of a filled cache (``prefill``): pick a token, mask
+        the rows that are finished, ``decode_step``. The greedy loop reads nothing back from the device."""
+        B, dev = logits.shape[0], logits.device
+        out = torch.empty(B, max_new_tokens, dtype=torch.int64, device=dev)
+        finished = torch.zeros(B, dtype=torch.bool, device=dev)
+        eos = None if eos_id is None else torch.full((), eos_id, dtype=torch.int64, device=dev)
+        for i in range(max_new_tokens):
+            if temperature == 0:
+                tok = logits.argmax(-1)
+            else:
+                z = logits.float() if logits.dtype in (torch.bfloat16, torch.float16) else logits
+                if top_k is not None and top_k < z.shape[-1]:
+                    kth = z.topk(top_k, dim=-1).values[:, -1:]
+                    z = z.masked_fill(z < kth, float("-inf"))
+                tok = torch.multinomial(torch.softmax(z / temperature, -1), 1, generator=generator).squeeze(1)
+            if eos is not None:
+                tok = torch.where(finished, eos, tok)
+                finished = finished | (tok == eos)
+            out[:, i] = tok
+            if i + 1 < max_new_tokens:
+                logits = self.decode_step(tok, cache)
+        return out
 
 
 def build(name: str, qk_norm: bool = False) -> Llama:

@@ -1,4 +1,5 @@
 // torch bindings of the decoder-LM kernels (csrc/kernels/lm.hip); shapes/dtypes validated on the host.
+#include <algorithm>
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -456,6 +457,60 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k, torch::Ten
   return {dq, dk, dv};
 }
 
+// decode attention (attn_decode.hip): q bf16 [B, Hq, D], caches bf16 [B, Smax, Hkv, D] whose inner three
+// dimensions are contiguous (the batch stride is free: cache[:, :n] is an operand), lens int32 [B] -> o like q.
+// splits: 0 = cs_attn_decode_splits(B, Hkv, Smax); anything else is clamped into [1, key tiles of Smax].
+torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, torch::Tensor lens, double scale,
+                          int64_t splits) {
+  for (auto* t : {&q, &kc, &vc, &lens}) TORCH_CHECK(t->is_cuda(), "attn_decode: all tensors must be GPU tensors");
+  for (auto* t : {&kc, &vc, &lens})
+    TORCH_CHECK(t->device() == q.device(), "attn_decode: all tensors must be on one device");
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16 && kc.scalar_type() == at::kBFloat16 &&
+                  vc.scalar_type() == at::kBFloat16, "attn_decode: q and the caches must be bfloat16");
+  TORCH_CHECK(q.dim() == 3, "attn_decode: q must be [B, Hq, D]");
+  TORCH_CHECK(kc.dim() == 4 && vc.dim() == 4 && kc.sizes() == vc.sizes(),
+              "attn_decode: the caches must be [B, Smax, Hkv, D] of one shape");
+  const int64_t B = q.size(0), Hq = q.size(1), D = q.size(2), Smax = kc.size(1), Hkv = kc.size(2);
+  TORCH_CHECK(kc.size(0) == B && kc.size(3) == D, "attn_decode: q and the caches must agree in B and D");
+  TORCH_CHECK(D == 64 || D == 128, "attn_decode: head_dim must be 64 or 128, got ", D);
+  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0 && (Hq / Hkv == 1 || Hq / Hkv == 2 || Hq / Hkv == 4 || Hq / Hkv == 8),
+              "attn_decode: query heads per kv head must be 1, 2, 4 or 8, got Hq ", Hq, ", Hkv ", Hkv);
+  TORCH_CHECK(Smax >= 1, "attn_decode: the caches need at least one position");
+  TORCH_CHECK(lens.scalar_type() == at::kInt, "attn_decode: lens must be int32, got ", lens.scalar_type());
+  TORCH_CHECK(lens.dim() == 1 && lens.size(0) == B && lens.is_contiguous(), "attn_decode: lens must be a contiguous [B]");
+  TORCH_CHECK(q.is_contiguous(), "attn_decode: q must be contiguous");
+  int64_t bstride = Smax * Hkv * D;
+  for (auto* t : {&kc, &vc}) {
+    TORCH_CHECK(t->stride(3) == 1 && t->stride(2) == D && t->stride(1) == Hkv * D,
+                "attn_decode: the inner three dimensions of the caches must be contiguous");
+    TORCH_CHECK(B <= 1 || (t->stride(0) >= Smax * Hkv * D && t->stride(0) % 8 == 0),
+                "attn_decode: the batch stride of a cache must be a multiple of 8 and hold Smax rows");
+  }
+  if (B > 1) {
+    TORCH_CHECK(kc.stride(0) == vc.stride(0), "attn_decode: the caches must have one batch stride");
+    bstride = kc.stride(0);
+  }
+  TORCH_CHECK(B <= 65535 && Hkv <= 65535 && Smax <= INT_MAX, "attn_decode: B, Hkv or Smax too large");
+  check_aligned(q, "q"); check_aligned(kc, "k_cache"); check_aligned(vc, "v_cache");
+  DevGuard g(q.device());
+  auto o = torch::empty_like(q);
+  if (B == 0) return o;
+  const int64_t tiles = cs_attn_decode_max_splits((int)Smax);
+  const int nsplit = splits == 0 ? cs_attn_decode_splits((int)B, (int)Hkv, (int)Smax)
+                                 : (int)std::min<int64_t>(std::max<int64_t>(splits, 1), tiles);
+  torch::Tensor ws;
+  float* wsp = nullptr;
+  if (nsplit > 1) {
+    ws = torch::empty({(int64_t)cs_attn_decode_ws_floats((int)B, (int)Hq, (int)D, nsplit)},
+                      q.options().dtype(at::kFloat));
+    wsp = ws.data_ptr<float>();
+  }
+  check_aligned(o, "o");
+  CS_LAUNCH(cs_attn_decode(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), lens.data_ptr<int>(), o.data_ptr(), wsp, (int)B,
+                           (int)Smax, (int)Hq, (int)Hkv, (int)D, (size_t)bstride, nsplit, (float)scale, cur_stream()));
+  return o;
+}
+
 // C = a @ b on the bf16 matrix cores (gemm_bf16.hip). a: [M, K], b: [K, N], bf16, each with unit
 // stride along one of its two dimensions (so x @ w.t(), dy @ w and dy.t() @ x all run without a
 // copy); out: a new bf16 (out_f32 false) or fp32 [M, N] tensor, or `acc` [M, N] += a @ b (fp32, or
@@ -581,6 +636,17 @@ void register_lm_ops(pybind11::module& m) {
   m.def("attn_bwd", &attn_bwd, "flash attention backward -> dq, dk, dv", py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("o"), py::arg("lse"), py::arg("dout"), py::arg("scale"), py::arg("causal"),
         py::arg("kstart") = c10::nullopt, py::arg("qend") = c10::nullopt);
+  m.def("attn_decode", &attn_decode,
+        "decode attention: q bf16 [B,Hq,D] against caches bf16 [B,Smax,Hkv,D] up to lens int32 [B] -> o [B,Hq,D]; "
+        "splits 0: decode_splits(B, Hkv, Smax), otherwise clamped into [1, key tiles of Smax]",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("scale"), py::arg("splits") = 0);
+  m.def("decode_key_tile", &cs_attn_decode_key_tile, "keys a workgroup of the decode kernel reads per trip");
+  m.def("decode_splits", [](int64_t B, int64_t Hkv, int64_t Smax) {
+          TORCH_CHECK(B >= 0 && Hkv >= 0 && Smax >= 0 && B <= INT_MAX && Hkv <= INT_MAX && Smax <= INT_MAX,
+                      "decode_splits: sizes out of range");
+          return cs_attn_decode_splits((int)B, (int)Hkv, (int)Smax);
+        }, "the key splits attn_decode picks for these shapes (never from lens)", py::arg("B"), py::arg("Hkv"),
+        py::arg("Smax"));
   m.def("mm_bf16", &mm_bf16, "C = a @ b on the bf16 matrix cores", pybind11::arg("a"), pybind11::arg("b"),
         pybind11::arg("out_f32") = false, pybind11::arg("acc") = c10::nullopt, pybind11::arg("splits") = -1);
   m.def("mm_bf16_bn_stats", &mm_bf16_bn_stats, "a @ b (bf16) plus per-256-row-tile BatchNorm (mean, M2) of the result");

@@ -418,6 +418,19 @@ hipError_t cs_attn_fwd_doc(const void* q, const void* k, const void* v, void* o,
 hipError_t cs_attn_bwd_doc(const void* q, const void* k, const void* v, const void* o, const void* dout,
                            const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int S, int Hq, int Hkv,
                            int D, float scale, const int* kstart, const int* qend, hipStream_t stream);
+// decode attention against a KV cache, split over the keys (attn_decode.hip). q / o: bf16 [B, Hq, D]; kc / vc:
+// bf16 [B, Smax, Hkv, D] with row stride Hkv * D and batch stride `batch_stride` elements (% 8 == 0, so a
+// [:, :n] slice of a longer cache is an operand); lens: int32 [B] on the device, clamped into [0, Smax] in
+// the kernel (a row of length 0 gives zeros). D 64 or 128, Hq / Hkv in {1, 2, 4, 8}, all pointers 16-byte
+// aligned, 1 <= nsplit <= cs_attn_decode_max_splits(Smax); ws: cs_attn_decode_ws_floats floats (may be null
+// when nsplit == 1). hipErrorInvalidValue on anything else. Splits are combined in split order: no atomics.
+int cs_attn_decode_key_tile();
+int cs_attn_decode_max_splits(int Smax);            // the key tiles of Smax
+int cs_attn_decode_splits(int B, int Hkv, int Smax);  // the default split count, from the shapes alone
+size_t cs_attn_decode_ws_floats(int B, int Hq, int D, int nsplit);
+hipError_t cs_attn_decode(const void* q, const void* kc, const void* vc, const int* lens, void* o, float* ws, int B,
+                          int Smax, int Hq, int Hkv, int D, size_t batch_stride, int nsplit, float scale,
+                          hipStream_t stream);
 // training BatchNorm2d (+ residual add, + ReLU) on NCHW fp32 / bf16 activations (bn_nchw.hip).
 // stat: f32 [4, C] = scale, shift, mean, invstd (written by the forward, read by the backward);
 // part: f32 scratch of cs_bn_nchw_partials(N, C) floats; coef: f32 [3, C] scratch (backward).
