@@ -21,6 +21,7 @@ inside the RMSNorm that follows it (``ops.lm.add_rms_norm``).
 
 Inference: ``Llama.generate`` = ``prefill`` (the training blocks, k and v copied into an ``ops.attention.KVCache``)
 plus one ``decode_step`` per token (split-KV decode attention, ``ops.attention.decode_attention``; docs/decode_attention.md).
+``generate(..., kv_dtype="fp8")`` keeps the cache as e4m3fn codes with one fp32 scale per (token, kv head).
 """
 from __future__ import annotations
 
@@ -119,10 +120,14 @@ class Attention(nn.Module):
     def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, doc=None, kv_out=None) -> torch.Tensor:
         """``doc``: ``ops.attention.DocBounds`` of a packed batch (attention stays inside a document).
         ``kv_out``: a pair of cache tensors [B, Smax >= S, Hkv, hd] (``Llama.prefill``); the post-RoPE k and v
-        are copied into their first S positions."""
+        are copied into their first S positions. With the scales of an FP8 cache appended, ``(k_cache, v_cache,
+        k_scale, v_scale)``, they are quantised into them (``ops.attention.kv_cache_append``)."""
         B, S, _ = x.shape
         q, k, v = self._qkv(x, cos, sin)
-        if kv_out is not None:
+        if kv_out is not None and len(kv_out) == 4:
+            from ..ops.attention import kv_cache_append
+            kv_cache_append(*kv_out, k, v)
+        elif kv_out is not None:
             kv_out[0][:, :S].copy_(k)
             kv_out[1][:, :S].copy_(v)
         from ..ops.attention import attention, attention_ref, native_ok
@@ -136,18 +141,27 @@ class Attention(nn.Module):
         return self.wo(o.reshape(B, S, self.nh * self.hd))
 
     def decode(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor,
-               slot: torch.Tensor, lens: torch.Tensor, bound: int) -> torch.Tensor:
+               slot: torch.Tensor, lens: torch.Tensor, bound: int, k_scale: torch.Tensor = None,
+               v_scale: torch.Tensor = None, pos: torch.Tensor = None) -> torch.Tensor:
         """One new token per row against the cache. ``x``: [B, 1, dim]; ``cos`` / ``sin``: [B, hd/2], the table
         rows of every row's own position; ``kc`` / ``vc``: this layer's caches [B, Smax, Hkv, hd]; ``slot``:
         int64 [B], ``b * Smax + position`` where the new k and v rows go; ``lens``: int32 [B], the lengths
-        with the new token counted; ``bound``: a host-known upper bound of ``lens``."""
+        with the new token counted; ``bound``: a host-known upper bound of ``lens``. An FP8 cache comes with
+        this layer's scales ``k_scale`` / ``v_scale`` [B, Smax, Hkv] and ``pos`` int32 [B], the positions
+        themselves: the new rows are then quantised into the cache by one ``kv_cache_append``."""
         B = x.shape[0]
         # [B, 1, H, hd] read as [1, B, H, hd]: the batch stands in the sequence axis of the RoPE ops, so
         # row b is rotated by table row b
         q, k, v = self._qkv(x.reshape(1, B, -1), cos, sin)
+        from ..ops.attention import decode_attention, kv_cache_append
+        if k_scale is not None:
+            kv_cache_append(kc, vc, k_scale, v_scale, k.view(B, 1, self.nkv, self.hd), v.view(B, 1, self.nkv, self.hd),
+                            pos)
+            o = decode_attention(q.view(B, self.nh, self.hd), kc[:, :bound], vc[:, :bound], lens,
+                                 k_scale=k_scale[:, :bound], v_scale=v_scale[:, :bound])
+            return self.wo(o.reshape(B, 1, self.nh * self.hd))
         kc.view(-1, self.nkv, self.hd).index_copy_(0, slot, k.view(B, self.nkv, self.hd).to(kc.dtype))
         vc.view(-1, self.nkv, self.hd).index_copy_(0, slot, v.view(B, self.nkv, self.hd).to(vc.dtype))
-        from ..ops.attention import decode_attention
         o = decode_attention(q.view(B, self.nh, self.hd), kc[:, :bound], vc[:, :bound], lens)
         return self.wo(o.reshape(B, 1, self.nh * self.hd))
 
@@ -287,8 +301,10 @@ class Llama(nn.Module):
         self._tables(cache.k.shape[2], dev)  # once, at the cache's length: decode_step gathers from them
         cos, sin = self._tables(S, dev)
         h = self.tok_embeddings(tokens)
+        fp8 = cache.k_scale is not None
         for l, blk in enumerate(self.layers):
-            h = h + blk.attention(blk.attention_norm(h), cos, sin, kv_out=(cache.k[l], cache.v[l]))
+            kv_out = (cache.k[l], cache.v[l]) + ((cache.k_scale[l], cache.v_scale[l]) if fp8 else ())
+            h = h + blk.attention(blk.attention_norm(h), cos, sin, kv_out=kv_out)
             h = h + blk.feed_forward(blk.ffn_norm(h))
         last = (lens.long() - 1).clamp(min=0)
         h = h[torch.arange(B, device=dev), last].unsqueeze(1)  # [B, 1, dim], gathered on the device
@@ -300,8 +316,9 @@ class Llama(nn.Module):
         """Append one token per row and return the logits [B, V] of the next one. Row b's position is
         ``cache.lens[b]``, so rows may differ; every row must still have room (``lens[b] < Smax``: a full
         row's write is clamped onto its last position). Nothing is read back from the device: the RoPE
-        table rows are gathered by position, the new k and v rows are scattered by a device index, and the
-        attention runs over ``cache[:, :bound]`` with ``bound`` the host-known prompt length plus steps."""
+        table rows are gathered by position, the new k and v rows are scattered by a device index (an FP8
+        cache: quantised and stored by one kernel that takes the positions), and the attention runs over
+        ``cache[:, :bound]`` with ``bound`` the host-known prompt length plus steps."""
         B = tok.shape[0]
         Smax = cache.k.shape[2]
         if cache.bound >= Smax:
@@ -314,20 +331,26 @@ class Llama(nn.Module):
         lens = (pos + 1).int()
         bound = cache.bound + 1
         h = self.tok_embeddings(tok.view(B, 1))
+        fp8 = cache.k_scale is not None
+        pos32 = pos.int() if fp8 else None
         for l, blk in enumerate(self.layers):
-            h = h + blk.attention.decode(blk.attention_norm(h), cos, sin, cache.k[l], cache.v[l], slot, lens, bound)
+            scales = dict(k_scale=cache.k_scale[l], v_scale=cache.v_scale[l], pos=pos32) if fp8 else {}
+            h = h + blk.attention.decode(blk.attention_norm(h), cos, sin, cache.k[l], cache.v[l], slot, lens, bound,
+                                         **scales)
             h = h + blk.feed_forward(blk.ffn_norm(h))
         cache.lens, cache.bound = lens, bound
         return self.output(self.norm(h)).squeeze(1)
 
     @torch.no_grad()
     def generate(self, tokens: torch.Tensor, max_new_tokens: int, prompt_lens=None, temperature: float = 0.0,
-                 top_k=None, eos_id=None, generator=None) -> torch.Tensor:
+                 top_k=None, eos_id=None, generator=None, kv_dtype=None) -> torch.Tensor:
         """``int64 [B, max_new_tokens]``: the continuation of every row of ``tokens`` [B, S] (right-padded,
         ``prompt_lens`` int [B]), one ``prefill`` and then one ``decode_step`` per token. ``temperature == 0``
         is greedy argmax; otherwise a token is drawn (``torch.multinomial`` with ``generator``) from
         ``softmax(logits / temperature)``, restricted to the ``top_k`` largest logits when given. A row that
-        has emitted ``eos_id`` keeps emitting it (a device-side mask: no early exit, no synchronisation)."""
+        has emitted ``eos_id`` keeps emitting it (a device-side mask: no early exit, no synchronisation).
+        ``kv_dtype``: the cache's dtype; ``None`` is ``cache_dtype``, ``"fp8"`` or ``torch.float8_e4m3fn`` an FP8
+        cache (e4m3fn codes and one fp32 scale per token and kv head: about half the bytes of bf16)."""
         from ..ops.attention import KVCache
         B, S = tokens.shape
         if max_new_tokens < 0 or S + max_new_tokens > self.cfg.max_seq:
@@ -337,7 +360,13 @@ class Llama(nn.Module):
         dev = tokens.device
         if max_new_tokens == 0:
             return torch.empty(B, 0, dtype=torch.int64, device=dev)
-        cache = KVCache.allocate(self.cfg, B, S + max_new_tokens, dev, self.cache_dtype(dev))
+        if kv_dtype is None:
+            kv_dtype = self.cache_dtype(dev)
+        elif kv_dtype == "fp8":
+            kv_dtype = torch.float8_e4m3fn
+        elif not isinstance(kv_dtype, torch.dtype):
+            raise ValueError(f"generate: kv_dtype must be None, 'fp8' or a torch dtype, got {kv_dtype!r}")
+        cache = KVCache.allocate(self.cfg, B, S + max_new_tokens, dev, kv_dtype)
         logits = self.prefill(tokens, cache, prompt_lens)
         return self.decode_loop(logits, cache, max_new_tokens, temperature, top_k, eos_id, generator)
 

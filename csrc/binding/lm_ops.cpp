@@ -460,37 +460,61 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k, torch::Ten
 // decode attention (attn_decode.hip): q bf16 [B, Hq, D], caches bf16 [B, Smax, Hkv, D] whose inner three
 // dimensions are contiguous (the batch stride is free: cache[:, :n] is an operand), lens int32 [B] -> o like q.
 // splits: 0 = cs_attn_decode_splits(B, Hkv, Smax); anything else is clamped into [1, key tiles of Smax].
-torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, torch::Tensor lens, double scale,
-                          int64_t splits) {
-  for (auto* t : {&q, &kc, &vc, &lens}) TORCH_CHECK(t->is_cuda(), "attn_decode: all tensors must be GPU tensors");
+// With ks / vs (attn_decode_fp8) the caches are float8_e4m3fn and ks / vs fp32 [B, Smax, Hkv] their scales,
+// contiguous in their inner two dimensions, with one batch stride.
+torch::Tensor decode_impl(const char* name, torch::Tensor q, torch::Tensor kc, torch::Tensor vc, const torch::Tensor* ks,
+                          const torch::Tensor* vs, torch::Tensor lens, double scale, int64_t splits) {
+  const bool fp8 = ks != nullptr;
+  for (auto* t : {&q, &kc, &vc, &lens}) TORCH_CHECK(t->is_cuda(), name, ": all tensors must be GPU tensors");
   for (auto* t : {&kc, &vc, &lens})
-    TORCH_CHECK(t->device() == q.device(), "attn_decode: all tensors must be on one device");
-  TORCH_CHECK(q.scalar_type() == at::kBFloat16 && kc.scalar_type() == at::kBFloat16 &&
-                  vc.scalar_type() == at::kBFloat16, "attn_decode: q and the caches must be bfloat16");
-  TORCH_CHECK(q.dim() == 3, "attn_decode: q must be [B, Hq, D]");
-  TORCH_CHECK(kc.dim() == 4 && vc.dim() == 4 && kc.sizes() == vc.sizes(),
-              "attn_decode: the caches must be [B, Smax, Hkv, D] of one shape");
+    TORCH_CHECK(t->device() == q.device(), name, ": all tensors must be on one device");
+  if (fp8) {
+    TORCH_CHECK(q.scalar_type() == at::kBFloat16, name, ": q must be bfloat16");
+    TORCH_CHECK(kc.scalar_type() == at::kFloat8_e4m3fn && vc.scalar_type() == at::kFloat8_e4m3fn, name,
+                ": the caches must be float8_e4m3fn");
+  } else {
+    TORCH_CHECK(q.scalar_type() == at::kBFloat16 && kc.scalar_type() == at::kBFloat16 &&
+                    vc.scalar_type() == at::kBFloat16, name, ": q and the caches must be bfloat16");
+  }
+  TORCH_CHECK(q.dim() == 3, name, ": q must be [B, Hq, D]");
+  TORCH_CHECK(kc.dim() == 4 && vc.dim() == 4 && kc.sizes() == vc.sizes(), name,
+              ": the caches must be [B, Smax, Hkv, D] of one shape");
   const int64_t B = q.size(0), Hq = q.size(1), D = q.size(2), Smax = kc.size(1), Hkv = kc.size(2);
-  TORCH_CHECK(kc.size(0) == B && kc.size(3) == D, "attn_decode: q and the caches must agree in B and D");
-  TORCH_CHECK(D == 64 || D == 128, "attn_decode: head_dim must be 64 or 128, got ", D);
-  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0 && (Hq / Hkv == 1 || Hq / Hkv == 2 || Hq / Hkv == 4 || Hq / Hkv == 8),
-              "attn_decode: query heads per kv head must be 1, 2, 4 or 8, got Hq ", Hq, ", Hkv ", Hkv);
-  TORCH_CHECK(Smax >= 1, "attn_decode: the caches need at least one position");
-  TORCH_CHECK(lens.scalar_type() == at::kInt, "attn_decode: lens must be int32, got ", lens.scalar_type());
-  TORCH_CHECK(lens.dim() == 1 && lens.size(0) == B && lens.is_contiguous(), "attn_decode: lens must be a contiguous [B]");
-  TORCH_CHECK(q.is_contiguous(), "attn_decode: q must be contiguous");
-  int64_t bstride = Smax * Hkv * D;
+  TORCH_CHECK(kc.size(0) == B && kc.size(3) == D, name, ": q and the caches must agree in B and D");
+  TORCH_CHECK(D == 64 || D == 128, name, ": head_dim must be 64 or 128, got ", D);
+  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0 && (Hq / Hkv == 1 || Hq / Hkv == 2 || Hq / Hkv == 4 || Hq / Hkv == 8), name,
+              ": query heads per kv head must be 1, 2, 4 or 8, got Hq ", Hq, ", Hkv ", Hkv);
+  TORCH_CHECK(Smax >= 1, name, ": the caches need at least one position");
+  TORCH_CHECK(lens.scalar_type() == at::kInt, name, ": lens must be int32, got ", lens.scalar_type());
+  TORCH_CHECK(lens.dim() == 1 && lens.size(0) == B && lens.is_contiguous(), name, ": lens must be a contiguous [B]");
+  TORCH_CHECK(q.is_contiguous(), name, ": q must be contiguous");
+  int64_t bstride = Smax * Hkv * D, sstride = Smax * Hkv;
   for (auto* t : {&kc, &vc}) {
-    TORCH_CHECK(t->stride(3) == 1 && t->stride(2) == D && t->stride(1) == Hkv * D,
-                "attn_decode: the inner three dimensions of the caches must be contiguous");
-    TORCH_CHECK(B <= 1 || (t->stride(0) >= Smax * Hkv * D && t->stride(0) % 8 == 0),
-                "attn_decode: the batch stride of a cache must be a multiple of 8 and hold Smax rows");
+    TORCH_CHECK(t->stride(3) == 1 && t->stride(2) == D && t->stride(1) == Hkv * D, name,
+                ": the inner three dimensions of the caches must be contiguous");
+    TORCH_CHECK(B <= 1 || (t->stride(0) >= Smax * Hkv * D && t->stride(0) % 8 == 0), name,
+                ": the batch stride of a cache must be a multiple of 8 and hold Smax rows");
   }
   if (B > 1) {
-    TORCH_CHECK(kc.stride(0) == vc.stride(0), "attn_decode: the caches must have one batch stride");
+    TORCH_CHECK(kc.stride(0) == vc.stride(0), name, ": the caches must have one batch stride");
     bstride = kc.stride(0);
   }
-  TORCH_CHECK(B <= 65535 && Hkv <= 65535 && Smax <= INT_MAX, "attn_decode: B, Hkv or Smax too large");
+  if (fp8) {
+    for (auto* t : {ks, vs}) {
+      TORCH_CHECK(t->is_cuda() && t->device() == q.device() && t->scalar_type() == at::kFloat, name,
+                  ": the scales must be fp32 tensors on q's device");
+      TORCH_CHECK(t->dim() == 3 && t->size(0) == B && t->size(1) == Smax && t->size(2) == Hkv, name,
+                  ": the scales must be [B, Smax, Hkv]");
+      TORCH_CHECK(t->stride(2) == 1 && t->stride(1) == Hkv, name,
+                  ": the inner two dimensions of the scales must be contiguous");
+      TORCH_CHECK(B <= 1 || t->stride(0) >= Smax * Hkv, name, ": the batch stride of a scale must hold Smax rows");
+    }
+    if (B > 1) {
+      TORCH_CHECK(ks->stride(0) == vs->stride(0), name, ": the scales must have one batch stride");
+      sstride = ks->stride(0);
+    }
+  }
+  TORCH_CHECK(B <= 65535 && Hkv <= 65535 && Smax <= INT_MAX, name, ": B, Hkv or Smax too large");
   check_aligned(q, "q"); check_aligned(kc, "k_cache"); check_aligned(vc, "v_cache");
   DevGuard g(q.device());
   auto o = torch::empty_like(q);
@@ -506,9 +530,84 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, t
     wsp = ws.data_ptr<float>();
   }
   check_aligned(o, "o");
+  if (fp8) {
+    CS_LAUNCH(cs_attn_decode_fp8(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), ks->data_ptr<float>(),
+                                 vs->data_ptr<float>(), lens.data_ptr<int>(), o.data_ptr(), wsp, (int)B, (int)Smax,
+                                 (int)Hq, (int)Hkv, (int)D, (size_t)bstride, (size_t)sstride, nsplit, (float)scale,
+                                 cur_stream()));
+    return o;
+  }
   CS_LAUNCH(cs_attn_decode(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), lens.data_ptr<int>(), o.data_ptr(), wsp, (int)B,
                            (int)Smax, (int)Hq, (int)Hkv, (int)D, (size_t)bstride, nsplit, (float)scale, cur_stream()));
   return o;
+}
+
+torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, torch::Tensor lens, double scale,
+                          int64_t splits) {
+  return decode_impl("attn_decode", q, kc, vc, nullptr, nullptr, lens, scale, splits);
+}
+
+torch::Tensor attn_decode_fp8(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, torch::Tensor ks, torch::Tensor vs,
+                              torch::Tensor lens, double scale, int64_t splits) {
+  return decode_impl("attn_decode_fp8", q, kc, vc, &ks, &vs, lens, scale, splits);
+}
+
+// quantising append to an FP8 KV cache (kv_append_fp8.hip), in place: k / v bf16 [B, S, Hkv, D] contiguous ->
+// codes in kc / vc float8_e4m3fn [B, Smax, Hkv, D] and scales in ks / vs fp32 [B, Smax, Hkv] at positions
+// (pos ? pos[b] : 0) + s, clamped into [0, Smax - 1] in the kernel. pos: int32 [B] on the device.
+void kv_append_fp8(torch::Tensor kc, torch::Tensor vc, torch::Tensor ks, torch::Tensor vs, torch::Tensor k,
+                   torch::Tensor v, c10::optional<torch::Tensor> pos) {
+  for (auto* t : {&kc, &vc, &ks, &vs, &k, &v}) {
+    TORCH_CHECK(t->is_cuda(), "kv_append_fp8: all tensors must be GPU tensors");
+    TORCH_CHECK(t->device() == k.device(), "kv_append_fp8: all tensors must be on one device");
+  }
+  TORCH_CHECK(k.scalar_type() == at::kBFloat16 && v.scalar_type() == at::kBFloat16,
+              "kv_append_fp8: k and v must be bfloat16");
+  TORCH_CHECK(kc.scalar_type() == at::kFloat8_e4m3fn && vc.scalar_type() == at::kFloat8_e4m3fn,
+              "kv_append_fp8: the caches must be float8_e4m3fn");
+  TORCH_CHECK(ks.scalar_type() == at::kFloat && vs.scalar_type() == at::kFloat, "kv_append_fp8: the scales must be fp32");
+  TORCH_CHECK(k.dim() == 4 && k.sizes() == v.sizes() && k.is_contiguous() && v.is_contiguous(),
+              "kv_append_fp8: k and v must be contiguous [B, S, Hkv, D] of one shape");
+  const int64_t B = k.size(0), S = k.size(1), Hkv = k.size(2), D = k.size(3);
+  TORCH_CHECK(D == 64 || D == 128, "kv_append_fp8: head_dim must be 64 or 128, got ", D);
+  TORCH_CHECK(kc.dim() == 4 && kc.sizes() == vc.sizes() && kc.size(0) == B && kc.size(2) == Hkv && kc.size(3) == D,
+              "kv_append_fp8: the caches must be [B, Smax, Hkv, D] of one shape, agreeing with k in B, Hkv and D");
+  const int64_t Smax = kc.size(1);
+  TORCH_CHECK(Smax >= 1 && Hkv >= 1, "kv_append_fp8: the caches need at least one position and one head");
+  int64_t bstride = Smax * Hkv * D, sstride = Smax * Hkv;
+  for (auto* t : {&kc, &vc}) {
+    TORCH_CHECK(t->stride(3) == 1 && t->stride(2) == D && t->stride(1) == Hkv * D,
+                "kv_append_fp8: the inner three dimensions of the caches must be contiguous");
+    TORCH_CHECK(B <= 1 || (t->stride(0) >= Smax * Hkv * D && t->stride(0) % 8 == 0),
+                "kv_append_fp8: the batch stride of a cache must be a multiple of 8 and hold Smax rows");
+  }
+  for (auto* t : {&ks, &vs}) {
+    TORCH_CHECK(t->dim() == 3 && t->size(0) == B && t->size(1) == Smax && t->size(2) == Hkv,
+                "kv_append_fp8: the scales must be [B, Smax, Hkv]");
+    TORCH_CHECK(t->stride(2) == 1 && t->stride(1) == Hkv,
+                "kv_append_fp8: the inner two dimensions of the scales must be contiguous");
+    TORCH_CHECK(B <= 1 || t->stride(0) >= Smax * Hkv, "kv_append_fp8: the batch stride of a scale must hold Smax rows");
+  }
+  if (B > 1) {
+    TORCH_CHECK(kc.stride(0) == vc.stride(0) && ks.stride(0) == vs.stride(0),
+                "kv_append_fp8: the caches, and the scales, must have one batch stride");
+    bstride = kc.stride(0);
+    sstride = ks.stride(0);
+  }
+  const int* posp = nullptr;
+  if (pos.has_value()) {
+    TORCH_CHECK(pos->is_cuda() && pos->device() == k.device() && pos->scalar_type() == at::kInt && pos->dim() == 1 &&
+                    pos->size(0) == B && pos->is_contiguous(),
+                "kv_append_fp8: pos must be a contiguous int32 [B] on k's device");
+    posp = pos->data_ptr<int>();
+  }
+  TORCH_CHECK(B <= INT_MAX && S <= INT_MAX && Smax <= INT_MAX && Hkv <= INT_MAX, "kv_append_fp8: sizes too large");
+  check_aligned(k, "k"); check_aligned(v, "v"); check_aligned(kc, "k_cache"); check_aligned(vc, "v_cache");
+  if (B == 0 || S == 0) return;
+  DevGuard g(k.device());
+  CS_LAUNCH(cs_kv_append_fp8(k.data_ptr(), v.data_ptr(), posp, kc.data_ptr(), vc.data_ptr(), ks.data_ptr<float>(),
+                             vs.data_ptr<float>(), (int)B, (int)S, (int)Smax, (int)Hkv, (int)D, (size_t)bstride,
+                             (size_t)sstride, cur_stream()));
 }
 
 // C = a @ b on the bf16 matrix cores (gemm_bf16.hip). a: [M, K], b: [K, N], bf16, each with unit
@@ -640,6 +739,14 @@ void register_lm_ops(pybind11::module& m) {
         "decode attention: q bf16 [B,Hq,D] against caches bf16 [B,Smax,Hkv,D] up to lens int32 [B] -> o [B,Hq,D]; "
         "splits 0: decode_splits(B, Hkv, Smax), otherwise clamped into [1, key tiles of Smax]",
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("scale"), py::arg("splits") = 0);
+  m.def("attn_decode_fp8", &attn_decode_fp8,
+        "attn_decode against float8_e4m3fn caches with fp32 scales [B,Smax,Hkv] per (token, kv head)",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("lens"),
+        py::arg("scale"), py::arg("splits") = 0);
+  m.def("kv_append_fp8", &kv_append_fp8,
+        "quantise k, v bf16 [B,S,Hkv,D] into float8_e4m3fn caches and fp32 scales at pos[b] + s (clamped), in place",
+        py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("k"), py::arg("v"),
+        py::arg("pos") = c10::nullopt);
   m.def("decode_key_tile", &cs_attn_decode_key_tile, "keys a workgroup of the decode kernel reads per trip");
   m.def("decode_splits", [](int64_t B, int64_t Hkv, int64_t Smax) {
           TORCH_CHECK(B >= 0 && Hkv >= 0 && Smax >= 0 && B <= INT_MAX && Hkv <= INT_MAX && Smax <= INT_MAX,

@@ -431,6 +431,21 @@ size_t cs_attn_decode_ws_floats(int B, int Hq, int D, int nsplit);
 hipError_t cs_attn_decode(const void* q, const void* kc, const void* vc, const int* lens, void* o, float* ws, int B,
                           int Smax, int Hq, int Hkv, int D, size_t batch_stride, int nsplit, float scale,
                           hipStream_t stream);
+// the same against FP8 caches: kc / vc hold e4m3fn codes [B, Smax, Hkv, D] (batch stride in bytes, % 8 == 0),
+// ks / vs fp32 scales [B, Smax, Hkv] with row stride Hkv and batch stride `scale_batch_stride` floats; the
+// value of element i of a row is float(code[i]) * scale. Everything else as cs_attn_decode.
+hipError_t cs_attn_decode_fp8(const void* q, const void* kc, const void* vc, const float* ks, const float* vs,
+                              const int* lens, void* o, float* ws, int B, int Smax, int Hq, int Hkv, int D,
+                              size_t batch_stride, size_t scale_batch_stride, int nsplit, float scale,
+                              hipStream_t stream);
+// quantising append to an FP8 KV cache (kv_append_fp8.hip): k / v bf16 [B, S, Hkv, D] contiguous and 16-byte
+// aligned -> codes in kc / vc and one power-of-two fp32 scale per (token, kv head) in ks / vs (layouts as for
+// cs_attn_decode_fp8), one launch for both tensors. Token (b, s) goes to position (pos ? pos[b] : 0) + s,
+// clamped into [0, Smax - 1] in the kernel; of tokens the clamp folds onto one position the last is stored.
+// pos: int32 [B] on the device or null. D 64 or 128. hipErrorInvalidValue on anything else.
+hipError_t cs_kv_append_fp8(const void* k, const void* v, const int* pos, void* kc, void* vc, float* ks, float* vs,
+                            int B, int S, int Smax, int Hkv, int D, size_t batch_stride, size_t scale_batch_stride,
+                            hipStream_t stream);
 // training BatchNorm2d (+ residual add, + ReLU) on NCHW fp32 / bf16 activations (bn_nchw.hip).
 // stat: f32 [4, C] = scale, shift, mean, invstd (written by the forward, read by the backward);
 // part: f32 scratch of cs_bn_nchw_partials(N, C) floats; coef: f32 [3, C] scratch (backward).

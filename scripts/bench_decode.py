@@ -15,7 +15,14 @@ in turn, as the layers of a model do, so no call finds its keys in the 256 MiB l
 call before. Bytes are counted from the lengths: K and V read once per kv head, 2 * sum(lens) * Hkv * D * 2.
 Needs a GPU: there is no CPU fallback.
 
+  --kv fp8      (native arm) the caches are FP8: e4m3fn codes plus one fp32 scale per (token, kv head), written by
+                ops.attention.kv_cache_append; bytes are then 2 * sum(lens) * Hkv * (D + 4)
+  --arm append  the cache write of one decode step (one new token per row) at B in {1, 8, 64}, cache length 2048:
+                --kv bf16 times what Attention.decode does for a bf16 cache (.to and index_copy_ for k and for
+                v), --kv fp8 the one quantising kv_cache_append that replaces them
+
   python scripts/bench_decode.py --arm native --iters 50 --warmup 10
+  python scripts/bench_decode.py --arm native --kv fp8
   python scripts/bench_decode.py --summary results.jsonl   # median and range over the processes, the gate
 """
 import argparse
@@ -33,8 +40,8 @@ RAGGED = (64, 8192)
 HBM_GBPS = 6300.0  # the achievable HBM rate the fractions are quoted against
 
 
-def kv_bytes(lens) -> int:
-    return 2 * int(sum(lens)) * HKV * D * 2
+def kv_bytes(lens, kv="bf16") -> int:
+    return 2 * int(sum(lens)) * HKV * (D * 2 if kv == "bf16" else D + 4)
 
 
 def _timed(fns, warmup, iters):
@@ -84,7 +91,8 @@ def summary(path: str) -> int:
 
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arm", choices=["native", "sdpa"])
+    ap.add_argument("--arm", choices=["native", "sdpa", "append"])
+    ap.add_argument("--kv", choices=["bf16", "fp8"], default="bf16", help="the cache format (native and append arms)")
     ap.add_argument("--summary", metavar="JSONL", help="summarise the result lines of several processes")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
@@ -94,6 +102,8 @@ def main() -> int:
         return summary(a.summary)
     if a.arm is None:
         ap.error("--arm or --summary")
+    if a.arm == "sdpa" and a.kv != "bf16":
+        ap.error("--arm sdpa reads bf16 caches only")
     import torch
     import torch.nn.functional as F
     if not torch.cuda.is_available():
@@ -106,11 +116,51 @@ def main() -> int:
     gen = torch.Generator(device=dev).manual_seed(0)
     scale = 1.0 / math.sqrt(D)
     out = []
+    fp8 = a.kv == "fp8"
+
+    def quantised(kc, vc):
+        """(k codes, v codes, k scales, v scales) of a bf16 cache pair, through the append kernel"""
+        B, n = kc.shape[:2]
+        bufs = (torch.empty_like(kc, dtype=attention.FP8), torch.empty_like(vc, dtype=attention.FP8),
+                torch.empty(B, n, HKV, device=dev), torch.empty(B, n, HKV, device=dev))
+        attention.kv_cache_append(*bufs, kc, vc)
+        return bufs
+
+    if a.arm == "append":
+        n = 2048
+        for B in (1, 8, 64):
+            copies = 16  # the layers of a model: every call writes another cache
+            k = torch.randn(B, 1, HKV, D, device=dev, generator=gen).bfloat16()
+            v = torch.randn(B, 1, HKV, D, device=dev, generator=gen).bfloat16()
+            pos = torch.randint(0, n, (B,), device=dev, generator=gen).int()
+            slot = torch.arange(B, device=dev) * n + pos.long()
+            caches = [(torch.zeros(B, n, HKV, D, device=dev).bfloat16(), torch.zeros(B, n, HKV, D, device=dev).bfloat16())
+                      for _ in range(copies)]
+            if fp8:
+                caches = [quantised(kc, vc) for kc, vc in caches]
+                assert attention.kv_append_native_ok(*caches[0], k, v, pos)
+
+                def mk(bufs):
+                    return lambda: attention.kv_cache_append(*bufs, k, v, pos)
+            else:
+                def mk(bufs):
+                    kc, vc = bufs
+
+                    def write():  # the cache write of models.llama.Attention.decode
+                        kc.view(-1, HKV, D).index_copy_(0, slot, k.view(B, HKV, D).to(kc.dtype))
+                        vc.view(-1, HKV, D).index_copy_(0, slot, v.view(B, HKV, D).to(vc.dtype))
+                    return write
+            with torch.no_grad():
+                med, lo, hi = _timed([mk(c) for c in caches], a.warmup, a.iters)
+            out.append({"name": f"append_B{B}", "B": B, "us_median": round(med, 1), "us_min": round(lo, 1),
+                        "us_max": round(hi, 1)})
+        print(json.dumps({"arm": a.arm, "kv": a.kv, "kv_heads": HKV, "head_dim": D, "iters": a.iters, "shapes": out}))
+        return 0
     shapes = [(f"B{b}_L{n}", b, n, None) for b, n in UNIFORM]
     rag = torch.randint(1, RAGGED[1] + 1, (RAGGED[0],), generator=torch.Generator().manual_seed(1))
     shapes.append((f"ragged_B{RAGGED[0]}_L1..{RAGGED[1]}", RAGGED[0], RAGGED[1], rag))
     for name, B, n, ragged in shapes:
-        per = 2 * B * n * HKV * D * 2
+        per = kv_bytes([n] * B, a.kv)
         copies = max(1, min(64, -(-a.rotate_mib * 2**20 // per)))
         q = torch.randn(B, HQ, D, device=dev, generator=gen).bfloat16()
         caches = [(torch.randn(B, n, HKV, D, device=dev, generator=gen).bfloat16(),
@@ -118,7 +168,23 @@ def main() -> int:
         host_lens = [n] * B if ragged is None else ragged.tolist()
         lens = torch.tensor(host_lens, dtype=torch.int32, device=dev)
         assert attention.decode_native_ok(q, *caches[0], lens)
-        if a.arm == "native":
+        with torch.no_grad():  # the bf16 kernel's result: what every arm is compared with
+            if fp8:  # on the dequantised first cache (its values are bf16 numbers), then the bf16 caches go
+                ref = None
+                for i, (kc, vc) in enumerate(caches):
+                    caches[i] = quantised(kc, vc)
+                    if ref is None:
+                        deq = [attention.kv_dequantize(caches[0][j], caches[0][j + 2], torch.bfloat16) for j in (0, 1)]
+                        ref = attention.decode_attention(q, *deq, lens, scale).float()
+                        del deq
+                    del kc, vc
+                assert attention.decode_native_ok(q, *caches[0][:2], lens, *caches[0][2:])
+            else:
+                ref = attention.decode_attention(q, *caches[0], lens, scale).float()
+        if a.arm == "native" and fp8:
+            def mk(kc, vc, ks, vs):
+                return lambda: attention.decode_attention(q, kc, vc, lens, scale, k_scale=ks, v_scale=vs)
+        elif a.arm == "native":
             def mk(kc, vc):
                 return lambda: attention.decode_attention(q, kc, vc, lens, scale)
         else:
@@ -130,20 +196,19 @@ def main() -> int:
             def mk(kc, vc):
                 k4, v4 = kc.transpose(1, 2), vc.transpose(1, 2)
                 return lambda: F.scaled_dot_product_attention(q4, k4, v4, attn_mask=mask, scale=scale, enable_gqa=True)
-        fns = [mk(kc, vc) for kc, vc in caches]
+        fns = [mk(*c) for c in caches]
         with torch.no_grad():
-            # the two arms compute the same thing
-            ref = attention.decode_attention(q, *caches[0], lens, scale).float()
+            # the arms compute the same thing
             got = fns[0]().reshape(B, HQ, D).float()
             err = (got - ref).abs().max().item()
             assert err < 0.05, f"{name}: the arms disagree by {err}"
             med, lo, hi = _timed(fns, a.warmup, a.iters)
-        nbytes = kv_bytes(host_lens)
+        nbytes = kv_bytes(host_lens, a.kv)
         out.append({"name": name, "B": B, "len": n, "ragged": ragged is not None, "copies": copies,
                     "splits": native.C().decode_splits(B, HKV, n), "us_median": round(med, 1), "us_min": round(lo, 1),
                     "us_max": round(hi, 1), "kv_bytes": nbytes, "GBps": round(nbytes / med / 1e3, 1), "max_abs_diff": err})
         del caches, fns
-    print(json.dumps({"arm": a.arm, "heads": HQ, "kv_heads": HKV, "head_dim": D, "iters": a.iters, "shapes": out}))
+    print(json.dumps({"arm": a.arm, "kv": a.kv, "heads": HQ, "kv_heads": HKV, "head_dim": D, "iters": a.iters, "shapes": out}))
     return 0
 
 
