@@ -52,29 +52,39 @@ class FusedSGD(torch.optim.SGD):
                 continue
             if not ps[0].is_cuda:
                 return super().step()
-            mom = group["momentum"]
-            first = False
-            bufs = []
-            for p in ps:
-                st = self.state[p]
-                if st.get("momentum_buffer") is None:
-                    st["momentum_buffer"] = torch.zeros_like(p)
-                    first = True
-                bufs.append(st["momentum_buffer"])
-            gs = [p.grad for p in ps]
-            # a parameter with a live bf16 shadow (ops.lm.ShadowLinear) gets it rewritten by the same pass
-            shs = [_shadow_of(p) for p in ps]
-            key = tuple((p.data_ptr(), g.data_ptr(), b.data_ptr(), s.data_ptr() if s.numel() else 0)
-                        for p, g, b, s in zip(ps, gs, bufs, shs))
-            tab = self._tables.get(id(group))
-            if tab is None or tab[0] != key:
-                t = native.C().sgd_multi_table(ps, gs, bufs, shs)
-                nchunks = int(t[-1].item())
-                tab = (key, t, nchunks)
-                self._tables[id(group)] = tab
-            native.C().sgd_multi(tab[1], len(ps), tab[2], group["lr"], mom, group["weight_decay"],
-                                 group["dampening"], self.grad_scale, first and mom != 0)
+            # `first` (buf = d, the buffer is not read) is decided per parameter, as torch.optim.SGD does:
+            # a parameter whose first gradient arrives after the others' must not reset their momentum.
+            # One launch per group whenever all its parameters agree (every step but such a one); in
+            # the step where they differ the new parameters get a launch and a cached table of their own.
+            fresh = [p for p in ps if self.state[p].get("momentum_buffer") is None]
+            for p in fresh:
+                self.state[p]["momentum_buffer"] = torch.zeros_like(p)
+            if group["momentum"] == 0 or len(fresh) in (0, len(ps)):
+                self._launch(group, 0, ps, bool(fresh))
+            else:
+                new = {id(p) for p in fresh}
+                self._launch(group, 0, [p for p in ps if id(p) not in new], False)
+                self._launch(group, 1, fresh, True)
         return loss
+
+    def _launch(self, group, slot, ps, first):
+        """one fused update of ``ps`` (parameters of ``group`` that have a gradient and a buffer); the
+        device table is cached per (group, slot) and rebuilt when a pointer changes"""
+        mom = group["momentum"]
+        bufs = [self.state[p]["momentum_buffer"] for p in ps]
+        gs = [p.grad for p in ps]
+        # a parameter with a live bf16 shadow (ops.lm.ShadowLinear) gets it rewritten by the same pass
+        shs = [_shadow_of(p) for p in ps]
+        key = tuple((p.data_ptr(), g.data_ptr(), b.data_ptr(), s.data_ptr() if s.numel() else 0)
+                    for p, g, b, s in zip(ps, gs, bufs, shs))
+        tab = self._tables.get((id(group), slot))
+        if tab is None or tab[0] != key:
+            t = native.C().sgd_multi_table(ps, gs, bufs, shs)
+            nchunks = int(t[-1].item())
+            tab = (key, t, nchunks)
+            self._tables[(id(group), slot)] = tab
+        native.C().sgd_multi(tab[1], len(ps), tab[2], group["lr"], mom, group["weight_decay"],
+                             group["dampening"], self.grad_scale, first and mom != 0)
 
 
 class FusedAdamW(torch.optim.AdamW):

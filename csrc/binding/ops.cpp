@@ -234,6 +234,17 @@ void accumulate(torch::Tensor g, torch::Tensor t, double div) {
   CS_LAUNCH(cs_accumulate(g.data_ptr<float>(), t.data_ptr<float>(), g.numel(), (float)div, cur_stream()));
 }
 
+// The kernels index a logits row with the label: bounds-checked on the host side of the call, like
+// augment's gather indices (cheap: B values; the engine calls cs_linear_xent itself, so the read
+// is off the training step).
+void check_labels(const torch::Tensor& labels, int64_t C, const char* who) {
+  CS_CHECK_CONTIG(labels);
+  if (labels.numel() == 0) return;
+  auto mm = at::aminmax(labels);
+  TORCH_CHECK(std::get<0>(mm).item<int64_t>() >= 0 && std::get<1>(mm).item<int64_t>() < C, who,
+              ": label out of range [0, C)");
+}
+
 std::vector<torch::Tensor> linear_xent(torch::Tensor feat, torch::Tensor W, torch::Tensor bias, torch::Tensor labels,
                                        double gscale, bool backward) {
   for (auto* t : {&feat, &W, &bias}) { CS_CHECK_CUDA(*t); CS_CHECK_F32(*t); CS_CHECK_CONTIG(*t); }
@@ -242,7 +253,8 @@ std::vector<torch::Tensor> linear_xent(torch::Tensor feat, torch::Tensor W, torc
   TORCH_CHECK(feat.dim() == 2 && W.dim() == 2 && bias.dim() == 1 && feat.size(1) == W.size(1) &&
               W.size(0) == bias.size(0) && labels.size(0) == feat.size(0), "linear_xent: shapes");
   const int B = feat.size(0), K = feat.size(1), C = W.size(0);
-  TORCH_CHECK(C <= 16 && K % 4 == 0, "linear_xent: C <= 16 and K % 4 == 0");
+  TORCH_CHECK(C >= 1 && C <= 16 && K % 4 == 0, "linear_xent: 1 <= C <= 16 and K % 4 == 0");
+  check_labels(labels, C, "linear_xent");
   DevGuard gd(feat.device());
   auto loss = torch::empty({}, feat.options());
   auto correct = torch::empty({}, feat.options().dtype(at::kInt));
@@ -269,7 +281,8 @@ std::vector<torch::Tensor> softmax_xent(torch::Tensor logits, torch::Tensor labe
   CS_CHECK_CUDA(logits); CS_CHECK_F32(logits); CS_CHECK_CONTIG(logits); CS_CHECK_CUDA(labels);
   TORCH_CHECK(logits.dim() == 2 && labels.dim() == 1 && labels.size(0) == logits.size(0) &&
               labels.scalar_type() == at::kLong, "softmax_xent: shapes");
-  TORCH_CHECK(logits.size(1) <= 16, "softmax_xent: C <= 16");
+  TORCH_CHECK(logits.size(1) >= 1 && logits.size(1) <= 16, "softmax_xent: 1 <= C <= 16");
+  check_labels(labels, logits.size(1), "softmax_xent");
   DevGuard gd(logits.device());
   auto loss = torch::empty({}, logits.options());
   auto dl = torch::empty_like(logits);

@@ -107,6 +107,7 @@ def test_softmax_xent_matches_torch(dev):
     l, dl, c = native.softmax_xent(lg.detach(), y)
     torch.testing.assert_close(l, loss.detach(), rtol=1e-5, atol=1e-6)
     torch.testing.assert_close(dl, lg.grad, rtol=1e-5, atol=1e-7)
+    assert int(c) == int((lg.argmax(1) == y).sum())
 
 
 def test_flat_sync_root_combines_match_torch(dev):
