@@ -85,13 +85,27 @@ def conv_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, 
 
 
 def conv_dgrad(dz: torch.Tensor, w_ohwi: torch.Tensor, B: int, H: int, W: int, *, bm: int = 64, bn: int = 64,
-               splits: int = 1, bk: int = 16, stage: int = 0) -> torch.Tensor:
-    """dx[B*H*W, Cin] from dz[B*H*W, Cout] and OHWI weights."""
+               splits: int = 1, bk: int = 16, stage: int = 0, ered: Optional[dict] = None):
+    """dx[B*H*W, Cin] from dz[B*H*W, Cout] and OHWI weights.
+    ``ered``: the BN-backward partial sums of the block below (whose output gradient dx is), taken
+    in the GEMM epilogue or the split-K combine (CsConvArgs::ered): a dict of ``y`` (that block's
+    pre-BN output, [B, H, W, Cin], or [B, 2H, 2W, Cin] with ``pool``), ``st`` (its ``BNState``) and
+    ``pool``. The result is then ``(dx, part [P, Cin, 3], P)`` with one partial per tile of
+    ``conv_ered_rows`` rows of dx."""
     cout, _, _, cin = w_ohwi.shape
     dx = torch.empty(B * H * W, cin, device=dz.device, dtype=torch.float32)
+    kw = _f3_amax(stage, dz, w_ohwi)
+    part = None
+    if ered is not None:
+        rows = native.C().conv_ered_rows(9 * cout, bm, bk, splits)
+        P = (B * H * W + rows - 1) // rows
+        part = torch.empty(P, cin, 3, device=dz.device, dtype=torch.float32)
+        st = ered["st"]
+        kw.update(ered_y=ered["y"], ered_scale=st.scale, ered_shift=st.shift, ered_mean=st.mean,
+                  ered_invstd=st.invstd, ered_pool=bool(ered.get("pool", False)), ered_part=part)
     native.C().conv_gemm(DGRAD, None, w_ohwi, dz, None, dx, _ws(DGRAD, B, H, W, cin, cout, splits, dz.device), None,
-                         B, H, W, cin, cout, False, bm, bn, splits, bk, stage, **_f3_amax(stage, dz, w_ohwi))
-    return dx
+                         B, H, W, cin, cout, False, bm, bn, splits, bk, stage, **kw)
+    return dx if part is None else (dx, part, part.shape[0])
 
 
 def conv_wgrad(dz: torch.Tensor, x: torch.Tensor, cout: int, *, w_oihw: bool = False, bm: int = 64, bn: int = 64,
@@ -189,3 +203,22 @@ def bn_relu_pool_bwd(y: torch.Tensor, G: torch.Tensor, st: BNState, gamma: torch
     native.C().bn_bwd(y, G, B, H, W, C, pool, st.scale, st.shift, st.mean, st.invstd, gamma, part, coef, dgamma,
                       dbeta, dbias, dz)
     return dz, dgamma, dbeta, dbias
+
+
+def bn_relu_pool_bwd_tail(y: torch.Tensor, G: torch.Tensor, st: BNState, gamma: torch.Tensor, B: int, H: int, W: int,
+                          part: torch.Tensor, P: int, pool: bool = False, fused: bool = False):
+    """The finalize + apply half of the BN backward when the reduce already ran: ``part`` holds P
+    partials [P, C, 3] = (sum g, sum g*xhat, sum xhat), e.g. ``conv_dgrad(..., ered=)``'s.
+    -> (dz [B*H*W, C], dgamma, dbeta, dbias, coef [C, 3]). ``fused``: the single-launch tail
+    (C % 16 == 0), otherwise finalize and apply launches (the engine's default backward)."""
+    C = gamma.numel()
+    coef = torch.empty(C, 3, device=y.device)
+    dgamma, dbeta, dbias = (torch.empty(C, device=y.device) for _ in range(3))
+    dz = torch.empty(B * H * W, C, device=y.device)
+    if fused:
+        bnv = torch.stack([st.scale, st.shift, st.mean, st.invstd]).contiguous()
+        native.C().bn_bwd_tail_fused(y, G, B, H, W, C, pool, bnv, gamma, part, P, coef, dgamma, dbeta, dbias, dz)
+    else:
+        native.C().bn_bwd_tail(y, G, B, H, W, C, pool, st.scale, st.shift, st.mean, st.invstd, gamma, part, P, coef,
+                               dgamma, dbeta, dbias, dz)
+    return dz, dgamma, dbeta, dbias, coef

@@ -33,7 +33,10 @@ int64_t conv_gemm(int64_t mode, c10::optional<torch::Tensor> x, c10::optional<to
                   c10::optional<torch::Tensor> gamma, c10::optional<torch::Tensor> beta,
                   c10::optional<torch::Tensor> running_mean, c10::optional<torch::Tensor> running_var,
                   c10::optional<torch::Tensor> bnv, double momentum, double eps, c10::optional<torch::Tensor> amax_a,
-                  c10::optional<torch::Tensor> amax_b) {
+                  c10::optional<torch::Tensor> amax_b, c10::optional<torch::Tensor> ered_y,
+                  c10::optional<torch::Tensor> ered_scale, c10::optional<torch::Tensor> ered_shift,
+                  c10::optional<torch::Tensor> ered_mean, c10::optional<torch::Tensor> ered_invstd, bool ered_pool,
+                  c10::optional<torch::Tensor> ered_part) {
   TORCH_CHECK(mode >= 0 && mode <= 2, "conv_gemm: bad mode");
   TORCH_CHECK(pow2(H) && pow2(W) && pow2(Cin) && pow2(Cout) && Cin >= 4 && Cout >= 64 && B > 0,
               "conv_gemm: H, W, Cin, Cout must be powers of two (Cin>=4, Cout>=64)");
@@ -83,6 +86,27 @@ int64_t conv_gemm(int64_t mode, c10::optional<torch::Tensor> x, c10::optional<to
     a.fin.rmean = mptr(running_mean); a.fin.rvar = mptr(running_var);
     a.fin.momentum = (float)momentum; a.fin.eps = (float)eps;
     a.fin.bnv = mptr(bnv);
+  }
+  if (ered_part.has_value() && ered_part->defined()) {
+    // DGRAD: the BN-backward partial sums of the block below from the epilogue / split-K combine
+    // (CsConvArgs::ered); y is that block's pre-BN conv output at full resolution
+    TORCH_CHECK(mode == CS_CONV_DGRAD, "conv_gemm: ered rides a data gradient (DGRAD) only");
+    TORCH_CHECK(Cin % 4 == 0, "conv_gemm: ered needs Cin % 4 == 0");
+    TORCH_CHECK(!(fin_cnt.has_value() && fin_cnt->defined()), "conv_gemm: the in-launch backward finalize is not bound");
+    TORCH_CHECK(ered_y.has_value() && ered_y->defined() && ered_scale.has_value() && ered_scale->defined() &&
+                    ered_shift.has_value() && ered_shift->defined() && ered_mean.has_value() && ered_mean->defined() &&
+                    ered_invstd.has_value() && ered_invstd->defined(),
+                "conv_gemm: ered needs y, scale, shift, mean and invstd");
+    check_t(ered_y, pix * (ered_pool ? 4 : 1) * Cin, "ered_y");
+    check_t(ered_scale, Cin, "ered_scale"); check_t(ered_shift, Cin, "ered_shift");
+    check_t(ered_mean, Cin, "ered_mean"); check_t(ered_invstd, Cin, "ered_invstd");
+    const int64_t er = cs_conv_ered_rows(a.K, bm, bk, splits);
+    check_t(ered_part, ((a.M + er - 1) / er) * Cin * 3, "ered_part");
+    a.ered.y = cptr(ered_y); a.ered.scale = cptr(ered_scale); a.ered.shift = cptr(ered_shift);
+    a.ered.mean = cptr(ered_mean); a.ered.invstd = cptr(ered_invstd); a.ered.part = mptr(ered_part);
+    a.ered.B = B; a.ered.H = ered_pool ? 2 * H : H; a.ered.W = ered_pool ? 2 * W : W; a.ered.C = Cin;
+    a.ered.pool = ered_pool ? 1 : 0;
+    a.ered.P = (int)((a.M + er - 1) / er);
   }
   DevGuard g(out.device());
   a.x = cptr(x); a.w = cptr(w); a.dz = cptr(dz); a.bias = cptr(bias);
@@ -197,6 +221,49 @@ void bn_fused_bwd(torch::Tensor y, torch::Tensor G, int64_t B, int64_t H, int64_
                             dz.data_ptr<float>(), cur_stream()));
 }
 
+// shared host checks of the two tails: the reduce already ran, part holds P partials [P][C][3]
+void check_tail(const char* who, int64_t cmul, torch::Tensor& y, torch::Tensor& G, int64_t B, int64_t H, int64_t W,
+                int64_t C, bool pool, torch::Tensor& gamma, torch::Tensor& part, int64_t P, torch::Tensor& coef,
+                c10::optional<torch::Tensor>& dgamma, c10::optional<torch::Tensor>& dbeta,
+                c10::optional<torch::Tensor>& dbias, torch::Tensor& dz) {
+  TORCH_CHECK(B > 0 && H > 0 && W > 0 && C > 0 && C % cmul == 0 && C <= 1024 && P >= 1 &&
+                  (!pool || (H % 2 == 0 && W % 2 == 0)),
+              who, ": shape (C % ", cmul, " == 0, C <= 1024, P >= 1, even H and W with pool)");
+  check_t(y, B * H * W * C, "y");
+  check_t(G, B * (pool ? H / 2 : H) * (pool ? W / 2 : W) * C, "G");
+  check_t(gamma, C, "gamma"); check_t(part, P * C * 3, "part"); check_t(coef, C * 3, "coef");
+  check_t(dgamma, C, "dgamma"); check_t(dbeta, C, "dbeta"); check_t(dbias, C, "dbias");
+  check_t(dz, B * H * W * C, "dz");
+}
+
+void bn_bwd_tail(torch::Tensor y, torch::Tensor G, int64_t B, int64_t H, int64_t W, int64_t C, bool pool,
+                 torch::Tensor scale, torch::Tensor shift, torch::Tensor mean, torch::Tensor invstd,
+                 torch::Tensor gamma, torch::Tensor part, int64_t P, torch::Tensor coef,
+                 c10::optional<torch::Tensor> dgamma, c10::optional<torch::Tensor> dbeta,
+                 c10::optional<torch::Tensor> dbias, torch::Tensor dz) {
+  check_tail("bn_bwd_tail", 4, y, G, B, H, W, C, pool, gamma, part, P, coef, dgamma, dbeta, dbias, dz);
+  for (auto* t : {&scale, &shift, &mean, &invstd}) check_t(*t, C, "bn vec");
+  DevGuard g(y.device());
+  CS_LAUNCH(cs_bn_bwd_tail(y.data_ptr<float>(), G.data_ptr<float>(), B, H, W, C, pool ? 1 : 0,
+                           scale.data_ptr<float>(), shift.data_ptr<float>(), mean.data_ptr<float>(),
+                           invstd.data_ptr<float>(), gamma.data_ptr<float>(), part.data_ptr<float>(), (int)P,
+                           coef.data_ptr<float>(), mptr(dgamma), mptr(dbeta), mptr(dbias), dz.data_ptr<float>(),
+                           cur_stream()));
+}
+
+void bn_bwd_tail_fused(torch::Tensor y, torch::Tensor G, int64_t B, int64_t H, int64_t W, int64_t C, bool pool,
+                       torch::Tensor bnv, torch::Tensor gamma, torch::Tensor part, int64_t P, torch::Tensor coef,
+                       c10::optional<torch::Tensor> dgamma, c10::optional<torch::Tensor> dbeta,
+                       c10::optional<torch::Tensor> dbias, torch::Tensor dz) {
+  check_tail("bn_bwd_tail_fused", 16, y, G, B, H, W, C, pool, gamma, part, P, coef, dgamma, dbeta, dbias, dz);
+  check_t(bnv, 4 * C, "bnv");
+  DevGuard g(y.device());
+  CS_LAUNCH(cs_bn_bwd_tail_fused(y.data_ptr<float>(), G.data_ptr<float>(), B, H, W, C, pool ? 1 : 0,
+                                 bnv.data_ptr<float>(), gamma.data_ptr<float>(), part.data_ptr<float>(), (int)P,
+                                 coef.data_ptr<float>(), mptr(dgamma), mptr(dbeta), mptr(dbias), dz.data_ptr<float>(),
+                                 cur_stream()));
+}
+
 }  // namespace
 
 void register_conv_ops(pybind11::module& m) {
@@ -209,7 +276,15 @@ void register_conv_ops(pybind11::module& m) {
         py::arg("stage") = 0, py::arg("fin_cnt") = py::none(), py::arg("fin_grp") = py::none(),
         py::arg("gamma") = py::none(), py::arg("beta") = py::none(), py::arg("running_mean") = py::none(),
         py::arg("running_var") = py::none(), py::arg("bnv") = py::none(), py::arg("momentum") = 0.1,
-        py::arg("eps") = 1e-5, py::arg("amax_a") = py::none(), py::arg("amax_b") = py::none());
+        py::arg("eps") = 1e-5, py::arg("amax_a") = py::none(), py::arg("amax_b") = py::none(),
+        py::arg("ered_y") = py::none(), py::arg("ered_scale") = py::none(), py::arg("ered_shift") = py::none(),
+        py::arg("ered_mean") = py::none(), py::arg("ered_invstd") = py::none(), py::arg("ered_pool") = false,
+        py::arg("ered_part") = py::none());
+  m.def("conv_ered_rows", [](int64_t K, int64_t bm, int64_t bk, int64_t splits) {
+    return cs_conv_ered_rows((int)K, (int)bm, (int)bk, (int)splits);
+  }, "rows per BN-backward partial of a DGRAD conv_gemm launch carrying ered");
+  m.def("bn_bwd_tail", &bn_bwd_tail, "BN backward finalize + apply from P partials [P][C][3] (two launches)");
+  m.def("bn_bwd_tail_fused", &bn_bwd_tail_fused, "BN backward finalize + apply from P partials in one launch");
   m.def("bn_fin_sizes", [](int64_t T, int64_t C, int64_t nc) {
     return std::vector<int64_t>{cs_bn_fin_ints((int)T, (int)C, (int)nc), cs_bn_fin_grp_floats((int)T, (int)C, (int)nc)};
   }, "(ticket ints, group-partial floats) of an in-launch BN finalize over T row tiles, C channels, nc-wide column tiles");

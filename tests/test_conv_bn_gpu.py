@@ -241,7 +241,8 @@ def test_bn_eval(dev):
                                      (16, 16, 68, 2), (64, 16, 128, 16)])
 def test_bn_finalize_many_partials(dev, B, H, C, R):
     # thousands of row-tile partials (conv0's 4096 at B=64): the 8-channel / 1024-thread finalize
-    # (T >= 2048, C % 8 == 0), ragged last tiles, and the one-wave-per-channel fallback (C = 68)
+    # (T >= 512, C % 8 == 0; bn.hip kFinWideMin: of these cases only T = 4096 enters it, the edge
+    # itself is in test_bn_edges_gpu.py), ragged last tiles, and the one-wave-per-channel fallback (C = 68)
     from cs744_pytorch_distributed_tutorial_amd.ops import functional as Fn
     torch.manual_seed(B * C + R)
     y = torch.randn(B, C, H, H, dtype=torch.float64) * 3 + 1.5
