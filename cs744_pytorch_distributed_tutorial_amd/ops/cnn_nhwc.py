@@ -365,7 +365,9 @@ def bn_act_nhwc(bn: nn.BatchNorm2d, x: torch.Tensor, relu: bool = True,
         tiles = getattr(x, "_cs_bn_tiles", None)  # statistics from the producing GEMM, if any
         return _BnActNHWC.apply(x.contiguous(), bn.weight, bn.bias, residual, bn.running_mean, bn.running_var,
                                 bn.num_batches_tracked, float(bn.momentum), float(bn.eps), relu, tiles)
-    if bn.training:  # CPU training: the module itself on an NCHW view
+    if bn.training or not bn.affine or bn.running_var is None:
+        # CPU training, or an eval module without affine parameters / running statistics (it then
+        # normalises with batch statistics): the module itself on an NCHW view
         y = bn(x.permute(0, 3, 1, 2)).permute(0, 2, 3, 1)
     else:
         scale = bn.weight * torch.rsqrt(bn.running_var + bn.eps)

@@ -1,6 +1,8 @@
 // torch bindings of the channels-last CNN kernels (csrc/kernels/cnn_nhwc.hip). Activations are
 // contiguous [B, H, W, C] fp32 / bf16 GPU tensors; shapes, dtypes and the vector-width
 // preconditions are validated here, before any launch.
+#include <algorithm>
+
 #include "binding/torch_util.h"
 #include "kernels/launchers.h"
 
@@ -46,6 +48,12 @@ torch::Tensor conv_nhwc_bf16(int64_t mode, torch::Tensor a, torch::Tensor b, int
     TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->scalar_type() == at::kBFloat16 && t->dim() == 4,
                 "conv_nhwc_bf16: operands must be contiguous 4-D bfloat16 GPU tensors");
   TORCH_CHECK(R >= 1 && S >= 1 && stride >= 1 && pad >= 0, "conv_nhwc_bf16: geometry");
+  {  // the padded image holds the kernel at least once (Ho, Wo >= 1); a negative numerator would round
+     // towards zero in the output-size division below and pass for an output of one pixel
+    const int64_t h = mode == 0 ? a.size(1) : mode == 1 ? H : b.size(1), w = mode == 0 ? a.size(2) : mode == 1 ? W : b.size(2);
+    TORCH_CHECK(h >= 1 && w >= 1 && h + 2 * pad >= R && w + 2 * pad >= S,
+                "conv_nhwc_bf16: the padded input is smaller than the kernel (empty output)");
+  }
   CsConvNhwcArgs p{};
   p.R = (int)R;
   p.S = (int)S;
@@ -153,13 +161,34 @@ std::vector<torch::Tensor> bn_nhwc_fwd(torch::Tensor x, c10::optional<torch::Ten
 // -> {dx, dres (or undefined), dweight, dbias}
 std::vector<torch::Tensor> bn_nhwc_bwd(torch::Tensor dy, torch::Tensor x, c10::optional<torch::Tensor> res,
                                        c10::optional<torch::Tensor> w, torch::Tensor stat, bool relu, bool need_dres,
-                                       c10::optional<torch::Tensor> mask) {
+                                       c10::optional<torch::Tensor> mask, c10::optional<torch::Tensor> pool_pos,
+                                       c10::optional<int64_t> H, c10::optional<int64_t> W) {
   check_nhwc(x, "bn_nhwc_bwd");
   const int dt = act_dt(x, "bn_nhwc_bwd");
-  check_like(dy, x, "dy");
   const bool has_res = res.has_value() && res->defined();
-  if (has_res) check_like(*res, x, "res");
+  const bool has_pool = pool_pos.has_value() && pool_pos->defined();
   const int64_t C = x.size(3), M = x.numel() / C;
+  int64_t Ho = 0, Wo = 0;
+  if (has_pool) {
+    // the BatchNorm's output went through the 3x3/2 max-pool: dy is the pooled gradient and the
+    // pool's backward gather runs inside both passes (bwd_reduce_kernel / apply_bwd_kernel, POOL)
+    TORCH_CHECK(H.has_value() && W.has_value() && *H >= 1 && *W >= 1 && x.size(1) == *H && x.size(2) == *W,
+                "bn_nhwc_bwd: pool_pos needs H and W, the spatial size of x");
+    Ho = (*H - 1) / 2 + 1, Wo = (*W - 1) / 2 + 1;
+    TORCH_CHECK(pool_pos->is_cuda() && pool_pos->is_contiguous() && pool_pos->scalar_type() == at::kByte &&
+                    pool_pos->numel() == x.size(0) * Ho * Wo * C,
+                "bn_nhwc_bwd: pool_pos must be a contiguous uint8 GPU tensor of B * Ho * Wo * C window positions");
+    TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && dy.scalar_type() == x.scalar_type() && dy.dim() == 4 &&
+                    dy.size(0) == x.size(0) && dy.size(1) == Ho && dy.size(2) == Wo && dy.size(3) == C,
+                "bn_nhwc_bwd: with pool_pos, dy must be a contiguous [B, Ho, Wo, C] GPU tensor typed like x");
+    TORCH_CHECK(!has_res && !(mask.has_value() && mask->defined()) && !need_dres,
+                "bn_nhwc_bwd: the fused-pool backward takes no residual and no mask");
+    TORCH_CHECK(M > 0 && M < (int64_t(1) << 31), "bn_nhwc_bwd: the fused-pool backward indexes rows in 32 bits");
+  } else {
+    TORCH_CHECK(!H.has_value() && !W.has_value(), "bn_nhwc_bwd: H and W go with pool_pos");
+    check_like(dy, x, "dy");
+  }
+  if (has_res) check_like(*res, x, "res");
   check_param(w, C, "weight");
   TORCH_CHECK(stat.is_cuda() && stat.scalar_type() == at::kFloat && stat.numel() == 4 * C, "bn_nhwc_bwd: stat");
   const bool has_mask = mask.has_value() && mask->defined();
@@ -177,7 +206,9 @@ std::vector<torch::Tensor> bn_nhwc_bwd(torch::Tensor dy, torch::Tensor x, c10::o
   CS_LAUNCH(cs_bn_nhwc_bwd(dt, dy.data_ptr(), x.data_ptr(), has_res ? res->data_ptr() : nullptr, opt_ptr<float>(w),
                            stat.data_ptr<float>(), relu ? 1 : 0, dx.data_ptr(), need_dres ? dres.data_ptr() : nullptr,
                            dw.data_ptr<float>(), db.data_ptr<float>(), coef.data_ptr<float>(), part.data_ptr<float>(),
-                           M, (int)C, cur_stream(), has_mask ? mask->data_ptr<uint8_t>() : nullptr));
+                           M, (int)C, cur_stream(), has_mask ? mask->data_ptr<uint8_t>() : nullptr,
+                           has_pool ? pool_pos->data_ptr<uint8_t>() : nullptr, has_pool ? (int)*H : 0,
+                           has_pool ? (int)*W : 0, (int)Ho, (int)Wo));
   return {dx, dres, dw, db};
 }
 
@@ -292,7 +323,20 @@ void register_nhwc_ops(pybind11::module& m) {
         pybind11::arg("tiles") = c10::nullopt, pybind11::arg("tile_rows") = 256);
   m.def("bn_nhwc_bwd", &bn_nhwc_bwd, "its backward -> (dx, dres, dweight, dbias); mask: the forward's ReLU mask",
         pybind11::arg("dy"), pybind11::arg("x"), pybind11::arg("res"), pybind11::arg("w"), pybind11::arg("stat"), pybind11::arg("relu"),
-        pybind11::arg("need_dres"), pybind11::arg("mask") = pybind11::none());
+        pybind11::arg("need_dres"), pybind11::arg("mask") = pybind11::none(), pybind11::arg("pool_pos") = pybind11::none(),
+        pybind11::arg("H") = pybind11::none(), pybind11::arg("W") = pybind11::none());
+  m.def("conv_nhwc_splits",
+        [](int64_t mode, int64_t B, int64_t H, int64_t W, int64_t C, int64_t Co, int64_t R, int64_t S, int64_t stride,
+           int64_t pad) {
+          TORCH_CHECK(mode >= 0 && mode <= 2 && B >= 1 && H >= 1 && W >= 1 && C >= 1 && Co >= 1 && R >= 1 && S >= 1 &&
+                          stride >= 1 && pad >= 0 && std::max({B, H, W, C, Co, R, S, stride, pad}) < (int64_t(1) << 31),
+                      "conv_nhwc_splits: geometry");
+          return cs_conv_nhwc_splits((int)mode, (int)B, (int)H, (int)W, (int)C, (int)Co, (int)R, (int)S, (int)stride,
+                                     (int)pad);
+        },
+        "split-K slab count conv_nhwc_bf16 allocates for a shape (1 unless mode 2, the weight gradient)",
+        pybind11::arg("mode"), pybind11::arg("B"), pybind11::arg("H"), pybind11::arg("W"), pybind11::arg("C"), pybind11::arg("Co"),
+        pybind11::arg("R"), pybind11::arg("S"), pybind11::arg("stride"), pybind11::arg("pad"));
   m.def("bn_relu_maxpool_nhwc_fwd", &bn_relu_maxpool_nhwc_fwd,
         "training BatchNorm2d + ReLU + 3x3/2 max-pool, NHWC, the apply fused into the pool -> (y, pos, stat)");
   m.def("maxpool3s2_nhwc_fwd", &maxpool3s2_nhwc_fwd, "3x3/2 pad-1 max-pool, NHWC -> (y, window position)");
