@@ -457,6 +457,34 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k, torch::Ten
   return {dq, dk, dv};
 }
 
+// The layout the KV-cache kernels take: kc / vc [B, Smax, Hkv, D] of one shape (checked by the caller), their inner
+// three dimensions contiguous, one batch stride that holds Smax rows and is a multiple of 8; and, where there are
+// scales (ks / vs not null), ks / vs [B, Smax, Hkv], their inner two dimensions contiguous, one batch stride that
+// holds Smax rows. Returns the batch strides of the caches and of the scales (of contiguous ones for B <= 1,
+// where torch's stride is free).
+std::pair<int64_t, int64_t> check_kv_layout(const char* name, const torch::Tensor& kc, const torch::Tensor& vc,
+                                            const torch::Tensor* ks, const torch::Tensor* vs) {
+  const int64_t B = kc.size(0), Smax = kc.size(1), Hkv = kc.size(2), D = kc.size(3);
+  for (auto* t : {&kc, &vc}) {
+    TORCH_CHECK(t->stride(3) == 1 && t->stride(2) == D && t->stride(1) == Hkv * D, name,
+                ": the inner three dimensions of the caches must be contiguous");
+    TORCH_CHECK(B <= 1 || (t->stride(0) >= Smax * Hkv * D && t->stride(0) % 8 == 0), name,
+                ": the batch stride of a cache must be a multiple of 8 and hold Smax rows");
+  }
+  TORCH_CHECK(B <= 1 || kc.stride(0) == vc.stride(0), name, ": the caches must have one batch stride");
+  const int64_t bstride = B > 1 ? kc.stride(0) : Smax * Hkv * D;
+  if (ks == nullptr) return {bstride, 0};
+  for (auto* t : {ks, vs}) {
+    TORCH_CHECK(t->dim() == 3 && t->size(0) == B && t->size(1) == Smax && t->size(2) == Hkv, name,
+                ": the scales must be [B, Smax, Hkv]");
+    TORCH_CHECK(t->stride(2) == 1 && t->stride(1) == Hkv, name,
+                ": the inner two dimensions of the scales must be contiguous");
+    TORCH_CHECK(B <= 1 || t->stride(0) >= Smax * Hkv, name, ": the batch stride of a scale must hold Smax rows");
+  }
+  TORCH_CHECK(B <= 1 || ks->stride(0) == vs->stride(0), name, ": the scales must have one batch stride");
+  return {bstride, B > 1 ? ks->stride(0) : Smax * Hkv};
+}
+
 // decode attention (attn_decode.hip): q bf16 [B, Hq, D], caches bf16 [B, Smax, Hkv, D] whose inner three
 // dimensions are contiguous (the batch stride is free: cache[:, :n] is an operand), lens int32 [B] -> o like q.
 // splits: 0 = cs_attn_decode_splits(B, Hkv, Smax); anything else is clamped into [1, key tiles of Smax].
@@ -488,32 +516,12 @@ torch::Tensor decode_impl(const char* name, torch::Tensor q, torch::Tensor kc, t
   TORCH_CHECK(lens.scalar_type() == at::kInt, name, ": lens must be int32, got ", lens.scalar_type());
   TORCH_CHECK(lens.dim() == 1 && lens.size(0) == B && lens.is_contiguous(), name, ": lens must be a contiguous [B]");
   TORCH_CHECK(q.is_contiguous(), name, ": q must be contiguous");
-  int64_t bstride = Smax * Hkv * D, sstride = Smax * Hkv;
-  for (auto* t : {&kc, &vc}) {
-    TORCH_CHECK(t->stride(3) == 1 && t->stride(2) == D && t->stride(1) == Hkv * D, name,
-                ": the inner three dimensions of the caches must be contiguous");
-    TORCH_CHECK(B <= 1 || (t->stride(0) >= Smax * Hkv * D && t->stride(0) % 8 == 0), name,
-                ": the batch stride of a cache must be a multiple of 8 and hold Smax rows");
-  }
-  if (B > 1) {
-    TORCH_CHECK(kc.stride(0) == vc.stride(0), name, ": the caches must have one batch stride");
-    bstride = kc.stride(0);
-  }
   if (fp8) {
-    for (auto* t : {ks, vs}) {
+    for (auto* t : {ks, vs})
       TORCH_CHECK(t->is_cuda() && t->device() == q.device() && t->scalar_type() == at::kFloat, name,
                   ": the scales must be fp32 tensors on q's device");
-      TORCH_CHECK(t->dim() == 3 && t->size(0) == B && t->size(1) == Smax && t->size(2) == Hkv, name,
-                  ": the scales must be [B, Smax, Hkv]");
-      TORCH_CHECK(t->stride(2) == 1 && t->stride(1) == Hkv, name,
-                  ": the inner two dimensions of the scales must be contiguous");
-      TORCH_CHECK(B <= 1 || t->stride(0) >= Smax * Hkv, name, ": the batch stride of a scale must hold Smax rows");
-    }
-    if (B > 1) {
-      TORCH_CHECK(ks->stride(0) == vs->stride(0), name, ": the scales must have one batch stride");
-      sstride = ks->stride(0);
-    }
   }
+  const auto [bstride, sstride] = check_kv_layout(name, kc, vc, ks, vs);
   TORCH_CHECK(B <= 65535 && Hkv <= 65535 && Smax <= INT_MAX, name, ": B, Hkv or Smax too large");
   check_aligned(q, "q"); check_aligned(kc, "k_cache"); check_aligned(vc, "v_cache");
   DevGuard g(q.device());
@@ -574,26 +582,7 @@ void kv_append_fp8(torch::Tensor kc, torch::Tensor vc, torch::Tensor ks, torch::
               "kv_append_fp8: the caches must be [B, Smax, Hkv, D] of one shape, agreeing with k in B, Hkv and D");
   const int64_t Smax = kc.size(1);
   TORCH_CHECK(Smax >= 1 && Hkv >= 1, "kv_append_fp8: the caches need at least one position and one head");
-  int64_t bstride = Smax * Hkv * D, sstride = Smax * Hkv;
-  for (auto* t : {&kc, &vc}) {
-    TORCH_CHECK(t->stride(3) == 1 && t->stride(2) == D && t->stride(1) == Hkv * D,
-                "kv_append_fp8: the inner three dimensions of the caches must be contiguous");
-    TORCH_CHECK(B <= 1 || (t->stride(0) >= Smax * Hkv * D && t->stride(0) % 8 == 0),
-                "kv_append_fp8: the batch stride of a cache must be a multiple of 8 and hold Smax rows");
-  }
-  for (auto* t : {&ks, &vs}) {
-    TORCH_CHECK(t->dim() == 3 && t->size(0) == B && t->size(1) == Smax && t->size(2) == Hkv,
-                "kv_append_fp8: the scales must be [B, Smax, Hkv]");
-    TORCH_CHECK(t->stride(2) == 1 && t->stride(1) == Hkv,
-                "kv_append_fp8: the inner two dimensions of the scales must be contiguous");
-    TORCH_CHECK(B <= 1 || t->stride(0) >= Smax * Hkv, "kv_append_fp8: the batch stride of a scale must hold Smax rows");
-  }
-  if (B > 1) {
-    TORCH_CHECK(kc.stride(0) == vc.stride(0) && ks.stride(0) == vs.stride(0),
-                "kv_append_fp8: the caches, and the scales, must have one batch stride");
-    bstride = kc.stride(0);
-    sstride = ks.stride(0);
-  }
+  const auto [bstride, sstride] = check_kv_layout("kv_append_fp8", kc, vc, &ks, &vs);
   const int* posp = nullptr;
   if (pos.has_value()) {
     TORCH_CHECK(pos->is_cuda() && pos->device() == k.device() && pos->scalar_type() == at::kInt && pos->dim() == 1 &&

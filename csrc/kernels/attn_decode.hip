@@ -4,11 +4,11 @@
 // argument, so cache[:, :n] of a longer cache is an operand); lens: int32 [B], sequence b sees keys
 // 0 .. lens[b] - 1 (clamped into [0, Smax] here). D in {64, 128}, G = Hq / Hkv in {1, 2, 4, 8}.
 //
-// attn_decode_kernel<D, G>, grid (nsplit, Hkv, B), one 256-thread workgroup per (slice of the keys, kv head,
-// sequence): it serves all G query heads of its kv head, so K and V are read from memory once per kv head.
-// A key row (D bf16) lies in D / 8 adjacent lanes, one 16-byte load per lane straight into VGPRs (no LDS
-// staging); a wave reads 64 / (D / 8) keys per load instruction and the workgroup a tile of kDecKT = 64 keys
-// per trip. The G dot products of a key are fp32 FMAs on the VALU, summed over the key's lanes by DPP
+// attn_decode_kernel<D, G, Cache>, grid (nsplit, Hkv, B), one 256-thread workgroup per (slice of the keys, kv
+// head, sequence): it serves all G query heads of its kv head, so K and V are read from memory once per kv head.
+// A key row (D elements) lies in D / 8 adjacent lanes, one load per lane straight into VGPRs (no LDS staging);
+// a wave reads 64 / (D / 8) keys per load instruction and the workgroup a tile of kDecKT = 64 keys per trip.
+// The G dot products of a key are fp32 FMAs on the VALU, summed over the key's lanes by DPP
 // (quad_perm, row_half_mirror, row_mirror: no LDS traffic); the matrix cores are not used: with at most 8
 // query rows an MFMA tile would be half padding, V would need a transpose through LDS for the second
 // product, and the kernel is bound by the K/V read, not by arithmetic. Every lane group keeps its own online
@@ -24,12 +24,14 @@
 // row in split order and writes bf16 o. With nsplit == 1 the first kernel writes o itself. No float atomics,
 // no arrival counters: the same bits every run.
 //
-// FP8 caches (attn_decode_fp8_kernel<D, G>, cs_attn_decode_fp8): kc / vc hold OCP e4m3fn codes, one byte each,
-// and ks / vs fp32 [B, Smax, Hkv] one power-of-two scale per (token, kv head); kv_append_fp8.hip writes both.
-// The lane mapping is the bf16 kernel's with half-width loads: a key row lies in the same D / 8 lanes, 8 bytes
-// per lane, unpacked two values at a time by v_cvt_pk_f32_fp8. The key's scale multiplies the finished score,
-// (q . k8) * ks, and the value's scale the weight, p * vs: G multiplies per key each, not D. A masked key loads
-// neither codes nor scales. The combine kernel and the split arithmetic are shared.
+// The cache format is the kernel's third template argument, and all that depends on it is in the two structs
+// below: the width of a lane's load, the unpack, and whether and where scales are read.
+//   Bf16Cache (cs_attn_decode): 16 bytes per lane, eight bf16 values.
+//   Fp8Cache (cs_attn_decode_fp8): kc / vc hold OCP e4m3fn codes, one byte each, and ks / vs fp32 [B, Smax, Hkv]
+//   one power-of-two scale per (token, kv head); kv_append_fp8.hip writes both. 8 bytes per lane, unpacked two
+//   values at a time by v_cvt_pk_f32_fp8. The key's scale multiplies the finished score, (q . k8) * ks, and the
+//   value's scale the weight, p * vs: G multiplies per key each, not D. A masked key loads neither codes nor
+//   scales. With power-of-two scales this is the arithmetic of the bf16 instantiation on the dequantised cache.
 #include <math.h>
 
 #include "common.h"
@@ -65,15 +67,41 @@ __device__ __forceinline__ void unpack8(const uint4& w, float (&f)[8]) {
   f[6] = __uint_as_float(w.w << 16); f[7] = __uint_as_float(w.w & 0xffff0000u);
 }
 
+// The cache formats. Row: what a lane loads of a key row, its eight elements; k / v and batch_stride count
+// elements; unpack: the eight values in fp32; kScaled: whether ks / vs [B, Smax, Hkv] hold a scale per row.
+struct Bf16Cache {
+  using Row = uint4;
+  static constexpr bool kScaled = false;
+  const __bf16 *k, *v;
+  size_t batch_stride;
+  static __device__ __forceinline__ void unpack(const Row& w, float (&f)[8]) { unpack8(w, f); }
+};
+
+struct Fp8Cache {
+  using Row = uint2;
+  static constexpr bool kScaled = true;
+  const unsigned char *k, *v;
+  size_t batch_stride;
+  const float *ks, *vs;
+  size_t scale_batch_stride;
+  // eight e4m3fn codes, two per v_cvt_pk_f32_fp8
+  static __device__ __forceinline__ void unpack(const Row& w, float (&f)[8]) {
+    const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.x, true);
+    const auto c = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.y, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.y, true);
+    f[0] = a[0]; f[1] = a[1]; f[2] = b[0]; f[3] = b[1];
+    f[4] = c[0]; f[5] = c[1]; f[6] = d[0]; f[7] = d[1];
+  }
+};
+
 // exp2(a - m) with m = -inf (nothing seen yet) read as 0: exp2(-inf - 0) = 0, never exp2(-inf + inf)
 __device__ __forceinline__ float safe_max(float m) { return m == -INFINITY ? 0.f : m; }
 
-template <int D, int G>
-__global__ __launch_bounds__(256) void attn_decode_kernel(const __bf16* __restrict__ q, const __bf16* __restrict__ kc,
-                                                          const __bf16* __restrict__ vc, const int* __restrict__ lens,
-                                                          __bf16* __restrict__ o, float* __restrict__ ws_o,
-                                                          float* __restrict__ ws_ml, int Smax, int Hkv,
-                                                          size_t batch_stride, float c) {
+template <int D, int G, typename Cache>
+__global__ __launch_bounds__(256) void attn_decode_kernel(const __bf16* __restrict__ q, const Cache cache,
+                                                          const int* __restrict__ lens, __bf16* __restrict__ o,
+                                                          float* __restrict__ ws_o, float* __restrict__ ws_ml,
+                                                          int Smax, int Hkv, float c) {
+  using Row = typename Cache::Row;
   constexpr int LPK = D / 8;                       // lanes per key row
   constexpr int KPW = 64 / LPK;                    // keys per wave load
   constexpr int U = kDecKT / (kDecWaves * KPW);    // loads of K (and of V) per lane and trip
@@ -104,33 +132,44 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const __bf16* __restri
   }
 
   const size_t row = (size_t)Hkv * D;
-  const size_t head = (size_t)b * batch_stride + (size_t)hkv * D + d0;
+  const size_t head = (size_t)b * cache.batch_stride + (size_t)hkv * D + d0;
+  size_t shead = 0;
+  if constexpr (Cache::kScaled) shead = (size_t)b * cache.scale_batch_stride + hkv;
   for (int t = t0; t < t1; ++t) {
-    uint4 kr[U], vr[U];
+    Row kr[U], vr[U];
+    float ksr[U], vsr[U];  // kScaled: the scales of the key's K and V rows, the same in all its lanes
     bool ok[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int key = t * kDecKT + u * (kDecWaves * KPW) + wave * KPW + r;
       ok[u] = key < len;
-      kr[u] = make_uint4(0, 0, 0, 0);
-      vr[u] = make_uint4(0, 0, 0, 0);
-      if (ok[u]) {  // key < len <= Smax: inside the cache; a masked key is not read at all
+      // Row(0u), not Row{}: value-initialisation makes the compiler schedule the bf16 instantiations differently,
+      // measurably slower at B 64 (docs/decode_attention.md, "Shared template")
+      kr[u] = Row(0u);
+      vr[u] = Row(0u);
+      ksr[u] = vsr[u] = 0.f;
+      if (ok[u]) {  // key < len <= Smax: inside the caches and the scales; a masked key reads neither
         const size_t off = head + (size_t)key * row;
-        kr[u] = *reinterpret_cast<const uint4*>(kc + off);
-        vr[u] = *reinterpret_cast<const uint4*>(vc + off);
+        kr[u] = *reinterpret_cast<const Row*>(cache.k + off);
+        vr[u] = *reinterpret_cast<const Row*>(cache.v + off);
+        if constexpr (Cache::kScaled) {
+          ksr[u] = cache.ks[shead + (size_t)key * Hkv];
+          vsr[u] = cache.vs[shead + (size_t)key * Hkv];
+        }
       }
     }
     float s[U][G];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       float kf[8];
-      unpack8(kr[u], kf);
+      Cache::unpack(kr[u], kf);
 #pragma unroll
       for (int g = 0; g < G; ++g) {
         float d = 0.f;
 #pragma unroll
         for (int j = 0; j < 8; ++j) d = fmaf(qf[g][j], kf[j], d);
         d = key_sum<LPK>(d);
+        if constexpr (Cache::kScaled) d *= ksr[u];  // the key's scale once per score
         s[u][g] = ok[u] ? d : -INFINITY;
       }
     }
@@ -155,11 +194,14 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const __bf16* __restri
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       float vf[8];
-      unpack8(vr[u], vf);
+      Cache::unpack(vr[u], vf);
 #pragma unroll
-      for (int g = 0; g < G; ++g)
+      for (int g = 0; g < G; ++g) {
+        float p = s[u][g];
+        if constexpr (Cache::kScaled) p *= vsr[u];  // the value's scale once per weight
 #pragma unroll
-        for (int j = 0; j < 8; ++j) acc[g][j] = fmaf(s[u][g], vf[j], acc[g][j]);
+        for (int j = 0; j < 8; ++j) acc[g][j] = fmaf(p, vf[j], acc[g][j]);
+      }
     }
   }
 
@@ -233,188 +275,15 @@ __global__ __launch_bounds__(D) void attn_decode_combine_kernel(const float* __r
   o[rowi * D + d] = (__bf16)(L > 0.f ? O / L : 0.f);
 }
 
-// ---------------------------------------------------------------- FP8 caches
-// eight e4m3fn codes, two per v_cvt_pk_f32_fp8
-__device__ __forceinline__ void unpack8_fp8(const uint2& w, float (&f)[8]) {
-  const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.x, true);
-  const auto c = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.y, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.y, true);
-  f[0] = a[0]; f[1] = a[1]; f[2] = b[0]; f[3] = b[1];
-  f[4] = c[0]; f[5] = c[1]; f[6] = d[0]; f[7] = d[1];
-}
-
-// attn_decode_kernel against e4m3fn caches with one fp32 scale per (key, kv head): the same grid, slices, lane
-// mapping (a key row in D / 8 lanes, now 8 bytes per lane), online softmax and merges. It is a copy and not an
-// instantiation of one template so that the bf16 kernels above keep their code objects bit for bit (the
-// shared form moved attn_decode_kernel<128, 8> from 254 to 252 VGPRs); what differs is marked "FP8:".
-template <int D, int G>
-__global__ __launch_bounds__(256) void attn_decode_fp8_kernel(
-    const __bf16* __restrict__ q, const unsigned char* __restrict__ kc, const unsigned char* __restrict__ vc,
-    const float* __restrict__ ks, const float* __restrict__ vs, const int* __restrict__ lens, __bf16* __restrict__ o,
-    float* __restrict__ ws_o, float* __restrict__ ws_ml, int Smax, int Hkv, size_t batch_stride,
-    size_t scale_batch_stride, float c) {
-  constexpr int LPK = D / 8;                       // lanes per key row
-  constexpr int KPW = 64 / LPK;                    // keys per wave load
-  constexpr int U = kDecKT / (kDecWaves * KPW);    // loads of K (and of V) per lane and trip
-  static_assert(U * kDecWaves * KPW == kDecKT, "tile");
-  __shared__ float sm_acc[kDecWaves][G][D];
-  __shared__ float sm_ml[kDecWaves][G][2];
-
-  const int split = blockIdx.x, nsplit = gridDim.x, hkv = blockIdx.y, b = blockIdx.z;
-  const int Hq = Hkv * G;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane / LPK, d0 = (lane % LPK) * 8;
-
-  int len = lens[b];
-  len = len < 0 ? 0 : (len > Smax ? Smax : len);
-  const int ntiles = (len + kDecKT - 1) / kDecKT;
-  const int base = ntiles / nsplit, rem = ntiles % nsplit;
-  const int t0 = split * base + (split < rem ? split : rem);
-  const int t1 = t0 + base + (split < rem ? 1 : 0);
-
-  float qf[G][8], m[G], l[G], acc[G][8];
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    const uint4 w = *reinterpret_cast<const uint4*>(q + ((size_t)b * Hq + (size_t)hkv * G + g) * D + d0);
-    unpack8(w, qf[g]);
-    m[g] = -INFINITY;
-    l[g] = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { qf[g][j] *= c; acc[g][j] = 0.f; }
-  }
-
-  const size_t row = (size_t)Hkv * D;  // FP8: bytes
-  const size_t head = (size_t)b * batch_stride + (size_t)hkv * D + d0;
-  const size_t shead = (size_t)b * scale_batch_stride + hkv;
-  for (int t = t0; t < t1; ++t) {
-    uint2 kr[U], vr[U];
-    float ksr[U], vsr[U];  // FP8: the scales of the key's K and V rows, the same in all its lanes
-    bool ok[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int key = t * kDecKT + u * (kDecWaves * KPW) + wave * KPW + r;
-      ok[u] = key < len;
-      kr[u] = make_uint2(0, 0);
-      vr[u] = make_uint2(0, 0);
-      ksr[u] = vsr[u] = 0.f;
-      if (ok[u]) {  // key < len <= Smax: inside the caches and the scales; a masked key reads neither
-        const size_t off = head + (size_t)key * row;
-        kr[u] = *reinterpret_cast<const uint2*>(kc + off);
-        vr[u] = *reinterpret_cast<const uint2*>(vc + off);
-        ksr[u] = ks[shead + (size_t)key * Hkv];
-        vsr[u] = vs[shead + (size_t)key * Hkv];
-      }
-    }
-    float s[U][G];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      float kf[8];
-      unpack8_fp8(kr[u], kf);
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        float d = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) d = fmaf(qf[g][j], kf[j], d);
-        d = key_sum<LPK>(d) * ksr[u];  // FP8: the key's scale once per score
-        s[u][g] = ok[u] ? d : -INFINITY;
-      }
-    }
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      float mx = m[g];
-#pragma unroll
-      for (int u = 0; u < U; ++u) mx = fmaxf(mx, s[u][g]);
-      const float ms = safe_max(mx);
-      const float alpha = __builtin_amdgcn_exp2f(m[g] - ms);
-      float ps = 0.f;
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        s[u][g] = __builtin_amdgcn_exp2f(s[u][g] - ms);
-        ps += s[u][g];
-      }
-      l[g] = l[g] * alpha + ps;
-      m[g] = mx;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[g][j] *= alpha;
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      float vf[8];
-      unpack8_fp8(vr[u], vf);
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        const float p = s[u][g] * vsr[u];  // FP8: the value's scale once per weight
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[g][j] = fmaf(p, vf[j], acc[g][j]);
-      }
-    }
-  }
-
-  // the lane groups of a wave: a butterfly over the group index; group 0's result is the wave's
-#pragma unroll
-  for (int off = LPK; off < 64; off <<= 1) {
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      const float m2 = __shfl_xor(m[g], off, 64), l2 = __shfl_xor(l[g], off, 64);
-      const float mx = fmaxf(m[g], m2), ms = safe_max(mx);
-      const float a1 = __builtin_amdgcn_exp2f(m[g] - ms), a2 = __builtin_amdgcn_exp2f(m2 - ms);
-      l[g] = l[g] * a1 + l2 * a2;
-      m[g] = mx;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[g][j] = acc[g][j] * a1 + __shfl_xor(acc[g][j], off, 64) * a2;
-    }
-  }
-  if (r == 0) {
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) sm_acc[wave][g][d0 + j] = acc[g][j];
-      if (d0 == 0) { sm_ml[wave][g][0] = m[g]; sm_ml[wave][g][1] = l[g]; }
-    }
-  }
-  __syncthreads();
-  // the four waves, in wave order
-  for (int i = tid; i < G * D; i += 256) {
-    const int g = i / D, d = i % D;
-    float mx = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < kDecWaves; ++w) mx = fmaxf(mx, sm_ml[w][g][0]);
-    const float ms = safe_max(mx);
-    float L = 0.f, O = 0.f;
-#pragma unroll
-    for (int w = 0; w < kDecWaves; ++w) {
-      const float a = __builtin_amdgcn_exp2f(sm_ml[w][g][0] - ms);
-      L += sm_ml[w][g][1] * a;
-      O += sm_acc[w][g][d] * a;
-    }
-    const size_t hq = (size_t)b * Hq + (size_t)hkv * G + g;
-    if (nsplit == 1) {
-      o[hq * D + d] = (__bf16)(L > 0.f ? O / L : 0.f);
-    } else {
-      ws_o[(hq * nsplit + split) * D + d] = O;
-      if (d == 0) {
-        ws_ml[(hq * nsplit + split) * 2] = mx;
-        ws_ml[(hq * nsplit + split) * 2 + 1] = L;
-      }
-    }
-  }
-}
-
-// ks == nullptr: bf16 caches; otherwise e4m3fn caches with their scales
-template <int D, int G>
-hipError_t launch_decode(const void* q, const void* kc, const void* vc, const float* ks, const float* vs,
-                         const int* lens, void* o, float* ws, int B, int Smax, int Hkv, size_t batch_stride,
-                         size_t scale_batch_stride, int nsplit, float scale, hipStream_t st) {
+template <int D, int G, typename Cache>
+hipError_t launch_decode(const void* q, const Cache& cache, const int* lens, void* o, float* ws, int B, int Smax,
+                         int Hkv, int nsplit, float scale, hipStream_t st) {
   const size_t rows = (size_t)B * Hkv * G;
   float* ws_o = ws;
   float* ws_ml = ws == nullptr ? nullptr : ws + rows * nsplit * D;
   const float c = scale * 1.4426950408889634f;
-  if (ks == nullptr) {
-    hipLaunchKernelGGL((attn_decode_kernel<D, G>), dim3(nsplit, Hkv, B), dim3(256), 0, st, (const __bf16*)q,
-                       (const __bf16*)kc, (const __bf16*)vc, lens, (__bf16*)o, ws_o, ws_ml, Smax, Hkv, batch_stride, c);
-  } else {
-    hipLaunchKernelGGL((attn_decode_fp8_kernel<D, G>), dim3(nsplit, Hkv, B), dim3(256), 0, st, (const __bf16*)q,
-                       (const unsigned char*)kc, (const unsigned char*)vc, ks, vs, lens, (__bf16*)o, ws_o, ws_ml, Smax,
-                       Hkv, batch_stride, scale_batch_stride, c);
-  }
+  hipLaunchKernelGGL((attn_decode_kernel<D, G, Cache>), dim3(nsplit, Hkv, B), dim3(256), 0, st, (const __bf16*)q, cache,
+                     lens, (__bf16*)o, ws_o, ws_ml, Smax, Hkv, c);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || nsplit == 1) return e;
   hipLaunchKernelGGL(attn_decode_combine_kernel<D>, dim3((unsigned)rows), dim3(D), 0, st, ws_o, ws_ml, (__bf16*)o,
@@ -422,13 +291,11 @@ hipError_t launch_decode(const void* q, const void* kc, const void* vc, const fl
   return hipGetLastError();
 }
 
-template <int D>
-hipError_t launch_decode_g(int G, const void* q, const void* kc, const void* vc, const float* ks, const float* vs,
-                           const int* lens, void* o, float* ws, int B, int Smax, int Hkv, size_t batch_stride,
-                           size_t scale_batch_stride, int nsplit, float scale, hipStream_t st) {
+template <int D, typename Cache>
+hipError_t launch_decode_g(int G, const void* q, const Cache& cache, const int* lens, void* o, float* ws, int B,
+                           int Smax, int Hkv, int nsplit, float scale, hipStream_t st) {
 #define CS_DECODE_G(g) \
-  case g: return launch_decode<D, g>(q, kc, vc, ks, vs, lens, o, ws, B, Smax, Hkv, batch_stride, scale_batch_stride, \
-                                     nsplit, scale, st)
+  case g: return launch_decode<D, g>(q, cache, lens, o, ws, B, Smax, Hkv, nsplit, scale, st)
   switch (G) {
     CS_DECODE_G(1);
     CS_DECODE_G(2);
@@ -463,23 +330,20 @@ size_t cs_attn_decode_ws_floats(int B, int Hq, int D, int nsplit) {
 
 namespace {
 
-hipError_t decode_checked(const void* q, const void* kc, const void* vc, const float* ks, const float* vs,
-                          const int* lens, void* o, float* ws, int B, int Smax, int Hq, int Hkv, int D,
-                          size_t batch_stride, size_t scale_batch_stride, int nsplit, float scale, hipStream_t stream) {
+template <typename Cache>
+hipError_t decode_checked(const void* q, const Cache& cache, const int* lens, void* o, float* ws, int B, int Smax,
+                          int Hq, int Hkv, int D, int nsplit, float scale, hipStream_t stream) {
   if (B == 0) return hipSuccess;
   if (B < 0 || B > 65535 || Hkv < 1 || Hkv > 65535 || Hq < 1 || Hq % Hkv != 0 || Smax < 1) return hipErrorInvalidValue;
   if (nsplit < 1 || nsplit > cs_attn_decode_max_splits(Smax)) return hipErrorInvalidValue;
-  if (batch_stride % 8 != 0 || batch_stride < (size_t)Smax * Hkv * D) return hipErrorInvalidValue;
-  if (!aligned16(q) || !aligned16(kc) || !aligned16(vc) || !aligned16(o) || lens == nullptr) return hipErrorInvalidValue;
+  if (cache.batch_stride % 8 != 0 || cache.batch_stride < (size_t)Smax * Hkv * D) return hipErrorInvalidValue;
+  if (!aligned16(q) || !aligned16(cache.k) || !aligned16(cache.v) || !aligned16(o) || lens == nullptr)
+    return hipErrorInvalidValue;
   if (nsplit > 1 && !aligned16(ws)) return hipErrorInvalidValue;
   if ((size_t)B * Hq > 0x7fffffffu) return hipErrorInvalidValue;
   const int G = Hq / Hkv;
-  if (D == 128)
-    return launch_decode_g<128>(G, q, kc, vc, ks, vs, lens, o, ws, B, Smax, Hkv, batch_stride, scale_batch_stride,
-                                nsplit, scale, stream);
-  if (D == 64)
-    return launch_decode_g<64>(G, q, kc, vc, ks, vs, lens, o, ws, B, Smax, Hkv, batch_stride, scale_batch_stride,
-                               nsplit, scale, stream);
+  if (D == 128) return launch_decode_g<128>(G, q, cache, lens, o, ws, B, Smax, Hkv, nsplit, scale, stream);
+  if (D == 64) return launch_decode_g<64>(G, q, cache, lens, o, ws, B, Smax, Hkv, nsplit, scale, stream);
   return hipErrorInvalidValue;
 }
 
@@ -488,8 +352,8 @@ hipError_t decode_checked(const void* q, const void* kc, const void* vc, const f
 hipError_t cs_attn_decode(const void* q, const void* kc, const void* vc, const int* lens, void* o, float* ws, int B,
                           int Smax, int Hq, int Hkv, int D, size_t batch_stride, int nsplit, float scale,
                           hipStream_t stream) {
-  return decode_checked(q, kc, vc, nullptr, nullptr, lens, o, ws, B, Smax, Hq, Hkv, D, batch_stride, 0, nsplit, scale,
-                        stream);
+  const Bf16Cache cache{(const __bf16*)kc, (const __bf16*)vc, batch_stride};
+  return decode_checked(q, cache, lens, o, ws, B, Smax, Hq, Hkv, D, nsplit, scale, stream);
 }
 
 hipError_t cs_attn_decode_fp8(const void* q, const void* kc, const void* vc, const float* ks, const float* vs,
@@ -500,6 +364,6 @@ hipError_t cs_attn_decode_fp8(const void* q, const void* kc, const void* vc, con
                 reinterpret_cast<uintptr_t>(vs) % 4 != 0 || Smax < 1 || Hkv < 1 ||
                 scale_batch_stride < (size_t)Smax * Hkv))
     return hipErrorInvalidValue;
-  return decode_checked(q, kc, vc, ks, vs, lens, o, ws, B, Smax, Hq, Hkv, D, batch_stride, scale_batch_stride, nsplit,
-                        scale, stream);
+  const Fp8Cache cache{(const unsigned char*)kc, (const unsigned char*)vc, batch_stride, ks, vs, scale_batch_stride};
+  return decode_checked(q, cache, lens, o, ws, B, Smax, Hq, Hkv, D, nsplit, scale, stream);
 }

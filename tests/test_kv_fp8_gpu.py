@@ -291,6 +291,31 @@ def test_determinism_garbage_and_slices(dev, no_ref, splits):
     assert torch.equal(a, got)
 
 
+@pytest.mark.parametrize("splits", [1, 3])
+@pytest.mark.parametrize("heads", [(4, 4), (32, 8)], ids=lambda h: f"hq{h[0]}_hkv{h[1]}")
+@pytest.mark.parametrize("D", [64, 128])
+def test_same_bits_as_bf16_on_the_dequantised_cache(dev, no_ref, D, heads, splits):
+    """The two cache formats are instantiations of one kernel and the scales are powers of two, so a scale moves
+    only exponents: (q . k8) * ks is q . (k8 * ks) and p * vs * v8 is p * (v8 * vs), rounding for rounding. The
+    FP8 kernel therefore returns the bits of the bf16 kernel on the dequantised cache. Rows from randn keep every
+    intermediate far from the denormal range, where the two could part."""
+    att = _att()
+    Hq, Hkv = heads
+    T = _tile()
+    Smax = 4 * T + 3
+    g = torch.Generator().manual_seed(10 * D + Hq)
+    lens = torch.tensor([0, 1, T - 1, T, T + 1, Smax])[torch.randperm(B, generator=g)].int().to(dev)
+    q = torch.randn(B, Hq, D, generator=g).to(BF16).to(dev)
+    k, v = (torch.randn(B, Smax, Hkv, D, generator=g).to(BF16).to(dev) for _ in range(2))
+    kc, vc = torch.empty_like(k, dtype=FP8), torch.empty_like(v, dtype=FP8)
+    ks, vs = torch.empty(B, Smax, Hkv, device=dev), torch.empty(B, Smax, Hkv, device=dev)
+    att.kv_cache_append(kc, vc, ks, vs, k, v)
+    o8 = att.decode_attention(q, kc, vc, lens, splits=splits, k_scale=ks, v_scale=vs)
+    o16 = att.decode_attention(q, att.kv_dequantize(kc, ks, BF16), att.kv_dequantize(vc, vs, BF16), lens, splits=splits)
+    assert not torch.isnan(o8).any() and o8.abs().max() > 0
+    assert torch.equal(o8, o16)
+
+
 def test_host_checks_and_fallback(dev):
     att, C = _att(), _C()
     Smax, Hq, Hkv, D = 9, 4, 2, 64
