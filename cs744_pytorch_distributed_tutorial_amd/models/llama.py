@@ -121,10 +121,17 @@ class Attention(nn.Module):
         """``doc``: ``ops.attention.DocBounds`` of a packed batch (attention stays inside a document).
         ``kv_out``: a pair of cache tensors [B, Smax >= S, Hkv, hd] (``Llama.prefill``); the post-RoPE k and v
         are copied into their first S positions. With the scales of an FP8 cache appended, ``(k_cache, v_cache,
-        k_scale, v_scale)``, they are quantised into them (``ops.attention.kv_cache_append``)."""
+        k_scale, v_scale)``, they are quantised into them (``ops.attention.kv_cache_append``). An
+        ``ops.attention.PagedLayer`` (a layer of a ``PagedKVCache``) takes them through its block table, the first
+        ``counts[b]`` tokens of row b (``ops.attention.kv_cache_append_paged``)."""
         B, S, _ = x.shape
         q, k, v = self._qkv(x, cos, sin)
-        if kv_out is not None and len(kv_out) == 4:
+        from ..ops.attention import PagedLayer
+        if isinstance(kv_out, PagedLayer):
+            from ..ops.attention import kv_cache_append_paged
+            kv_cache_append_paged(kv_out.k, kv_out.v, kv_out.block_table, k, v, counts=kv_out.counts,
+                                  k_scale=kv_out.k_scale, v_scale=kv_out.v_scale)
+        elif kv_out is not None and len(kv_out) == 4:
             from ..ops.attention import kv_cache_append
             kv_cache_append(*kv_out, k, v)
         elif kv_out is not None:
@@ -163,6 +170,21 @@ class Attention(nn.Module):
         kc.view(-1, self.nkv, self.hd).index_copy_(0, slot, k.view(B, self.nkv, self.hd).to(kc.dtype))
         vc.view(-1, self.nkv, self.hd).index_copy_(0, slot, v.view(B, self.nkv, self.hd).to(vc.dtype))
         o = decode_attention(q.view(B, self.nh, self.hd), kc[:, :bound], vc[:, :bound], lens)
+        return self.wo(o.reshape(B, 1, self.nh * self.hd))
+
+
+    def decode_paged(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, layer, pos: torch.Tensor,
+                     lens: torch.Tensor) -> torch.Tensor:
+        """``decode`` against one layer of a ``PagedKVCache`` (``ops.attention.PagedLayer``, its table cut to the
+        columns the lengths can reach): one paged append of the new rows at ``pos`` int32 [B], then paged decode
+        attention up to ``lens`` int32 [B]."""
+        B = x.shape[0]
+        q, k, v = self._qkv(x.reshape(1, B, -1), cos, sin)
+        from ..ops.attention import decode_attention_paged, kv_cache_append_paged
+        kv_cache_append_paged(layer.k, layer.v, layer.block_table, k.view(B, 1, self.nkv, self.hd),
+                              v.view(B, 1, self.nkv, self.hd), pos, k_scale=layer.k_scale, v_scale=layer.v_scale)
+        o = decode_attention_paged(q.view(B, self.nh, self.hd), layer.k, layer.v, layer.block_table, lens,
+                                   k_scale=layer.k_scale, v_scale=layer.v_scale)
         return self.wo(o.reshape(B, 1, self.nh * self.hd))
 
 
@@ -284,11 +306,20 @@ class Llama(nn.Module):
         every value in [1, S] (default: all S). The blocks run with causal flash attention, which already
         keeps the padding out of the real positions; each layer's post-RoPE k and v go to ``cache[:, :S]``,
         ``cache.lens`` becomes ``prompt_lens``, and the final norm and the head run on the B last rows only.
-        Packed documents (``doc_ids``) have no cached form and are refused."""
+        Packed documents (``doc_ids``) have no cached form and are refused.
+
+        With an ``ops.attention.PagedKVCache`` the lengths are read to the host once, before the layers (the only
+        read-back; none when ``prompt_lens`` is a list or a host tensor), every row's slot is grown to its own
+        length and the table committed; each layer's k and v then go through the table, the first ``lens[b]``
+        tokens of row b only, so the padding takes no pages. The prompt's attention runs on the fresh projections
+        as before."""
         if doc_ids is not None:
             raise ValueError("prefill: a document mask (doc_ids) cannot be combined with a KV cache")
         if tokens.dim() != 2:
             raise ValueError("prefill: tokens must be [B, S]")
+        from ..ops.attention import PagedKVCache
+        if isinstance(cache, PagedKVCache):
+            return self._prefill_paged(tokens, cache, prompt_lens)
         B, S = tokens.shape
         if cache.k.shape[0] != len(self.layers) or cache.k.shape[1] != B or cache.k.shape[2] < S or S < 1:
             raise ValueError(f"prefill: the cache {tuple(cache.k.shape)} does not hold {len(self.layers)} layers of "
@@ -311,6 +342,52 @@ class Llama(nn.Module):
         cache.lens, cache.bound = lens, S
         return self.output(self.norm(h)).squeeze(1)
 
+    def _prefill_paged(self, tokens: torch.Tensor, cache, prompt_lens) -> torch.Tensor:
+        B, S = tokens.shape
+        if cache.k.shape[0] != len(self.layers) or cache.block_table.shape[0] != B or S < 1 or S > cache.max_len:
+            raise ValueError(f"prefill: a paged cache of {cache.k.shape[0]} layers, {cache.block_table.shape[0]} slots "
+                             f"and {cache.max_len} positions does not hold {len(self.layers)} layers of [{B}, {S}] "
+                             "tokens")
+        dev = tokens.device
+        host = [S] * B if prompt_lens is None else torch.as_tensor(prompt_lens).reshape(B).tolist()
+        host = [min(max(int(n), 0), S) for n in host]
+        for b, n in enumerate(host):
+            cache.reserve(b, n)
+        cache.commit()
+        lens = torch.tensor(host, dtype=torch.int32).to(dev)
+        self._tables(cache.max_len, dev)  # once, at the table's reach: decode_step gathers from them
+        cos, sin = self._tables(S, dev)
+        h = self.tok_embeddings(tokens)
+        for l, blk in enumerate(self.layers):
+            h = h + blk.attention(blk.attention_norm(h), cos, sin, kv_out=cache.layer(l, counts=lens))
+            h = h + blk.feed_forward(blk.ffn_norm(h))
+        last = (lens.long() - 1).clamp(min=0)
+        h = h[torch.arange(B, device=dev), last].unsqueeze(1)
+        cache.lens, cache.bound, cache.row_bound = lens, max(host), list(host)
+        return self.output(self.norm(h)).squeeze(1)
+
+    def _decode_step_paged(self, tok: torch.Tensor, cache) -> torch.Tensor:
+        B = tok.shape[0]
+        for b in range(B):  # host only; a step never allocates behind the caller's back
+            if cache.capacity(b) < cache.row_bound[b] + 1:
+                raise ValueError(f"decode_step: slot {b} holds {cache.capacity(b)} positions and needs "
+                                 f"{cache.row_bound[b] + 1}: call cache.reserve({b}, n) and cache.commit() first")
+        dev = tok.device
+        cos, sin = self._tables(cache.max_len, dev)
+        pos = cache.lens  # int32 [B]; a position outside the slot's pages is dropped by the append
+        rope = pos.long().clamp(0, cache.max_len - 1)
+        cos, sin = cos[rope], sin[rope]
+        lens = pos + 1
+        bound = cache.bound + 1
+        cols = -(-bound // cache.page_size)
+        h = self.tok_embeddings(tok.view(B, 1))
+        for l, blk in enumerate(self.layers):
+            h = h + blk.attention.decode_paged(blk.attention_norm(h), cos, sin, cache.layer(l, cols=cols), pos, lens)
+            h = h + blk.feed_forward(blk.ffn_norm(h))
+        cache.lens, cache.bound = lens, bound
+        cache.row_bound = [n + 1 for n in cache.row_bound]
+        return self.output(self.norm(h)).squeeze(1)
+
     @torch.no_grad()
     def decode_step(self, tok: torch.Tensor, cache) -> torch.Tensor:
         """Append one token per row and return the logits [B, V] of the next one. Row b's position is
@@ -318,7 +395,14 @@ class Llama(nn.Module):
         row's write is clamped onto its last position). Nothing is read back from the device: the RoPE
         table rows are gathered by position, the new k and v rows are scattered by a device index (an FP8
         cache: quantised and stored by one kernel that takes the positions), and the attention runs over
-        ``cache[:, :bound]`` with ``bound`` the host-known prompt length plus steps."""
+        ``cache[:, :bound]`` with ``bound`` the host-known prompt length plus steps.
+
+        With an ``ops.attention.PagedKVCache``: a host-only check that every slot's pages hold its own host bound
+        plus one (``ValueError`` naming ``reserve`` otherwise), one paged append at the lengths, and paged decode
+        attention over ``block_table[:, :ceil(bound / page)]``. No read-back and no table traffic in a step."""
+        from ..ops.attention import PagedKVCache
+        if isinstance(cache, PagedKVCache):
+            return self._decode_step_paged(tok, cache)
         B = tok.shape[0]
         Smax = cache.k.shape[2]
         if cache.bound >= Smax:
@@ -343,15 +427,22 @@ class Llama(nn.Module):
 
     @torch.no_grad()
     def generate(self, tokens: torch.Tensor, max_new_tokens: int, prompt_lens=None, temperature: float = 0.0,
-                 top_k=None, eos_id=None, generator=None, kv_dtype=None) -> torch.Tensor:
+                 top_k=None, eos_id=None, generator=None, kv_dtype=None, page_size=None, kv_pool=None) -> torch.Tensor:
         """``int64 [B, max_new_tokens]``: the continuation of every row of ``tokens`` [B, S] (right-padded,
         ``prompt_lens`` int [B]), one ``prefill`` and then one ``decode_step`` per token. ``temperature == 0``
         is greedy argmax; otherwise a token is drawn (``torch.multinomial`` with ``generator``) from
         ``softmax(logits / temperature)``, restricted to the ``top_k`` largest logits when given. A row that
         has emitted ``eos_id`` keeps emitting it (a device-side mask: no early exit, no synchronisation).
         ``kv_dtype``: the cache's dtype; ``None`` is ``cache_dtype``, ``"fp8"`` or ``torch.float8_e4m3fn`` an FP8
-        cache (e4m3fn codes and one fp32 scale per token and kv head: about half the bytes of bf16)."""
-        from ..ops.attention import KVCache
+        cache (e4m3fn codes and one fp32 scale per token and kv head: about half the bytes of bf16).
+
+        ``page_size``: an int builds a private ``PagedKVCache`` of exactly ``sum_b ceil((len_b + max_new_tokens) /
+        page_size)`` pages instead of the ``[B, S + max_new_tokens]`` slab. ``kv_pool``: a caller's
+        ``PagedKVCache`` with B slots, all free; ``len_b + max_new_tokens`` positions are reserved per row up front
+        (``RuntimeError`` when the pool cannot cover them) and the rows are freed before returning, also on an
+        exception; the pool's dtype is the cache's, and ``kv_dtype`` must be ``None`` or agree with it. With
+        neither argument the contiguous cache is used as before."""
+        from ..ops.attention import KVCache, PagedKVCache
         B, S = tokens.shape
         if max_new_tokens < 0 or S + max_new_tokens > self.cfg.max_seq:
             raise ValueError(f"generate: {S} prompt + {max_new_tokens} new tokens exceed max_seq {self.cfg.max_seq}")
@@ -360,15 +451,40 @@ class Llama(nn.Module):
         dev = tokens.device
         if max_new_tokens == 0:
             return torch.empty(B, 0, dtype=torch.int64, device=dev)
+        pool_any_dtype = kv_dtype is None  # a caller's pool: its own dtype stands unless kv_dtype names one
         if kv_dtype is None:
             kv_dtype = self.cache_dtype(dev)
         elif kv_dtype == "fp8":
             kv_dtype = torch.float8_e4m3fn
         elif not isinstance(kv_dtype, torch.dtype):
             raise ValueError(f"generate: kv_dtype must be None, 'fp8' or a torch dtype, got {kv_dtype!r}")
-        cache = KVCache.allocate(self.cfg, B, S + max_new_tokens, dev, kv_dtype)
-        logits = self.prefill(tokens, cache, prompt_lens)
-        return self.decode_loop(logits, cache, max_new_tokens, temperature, top_k, eos_id, generator)
+        if page_size is not None and kv_pool is not None:
+            raise ValueError("generate: pass page_size or kv_pool, not both")
+        if page_size is None and kv_pool is None:
+            cache = KVCache.allocate(self.cfg, B, S + max_new_tokens, dev, kv_dtype)
+            logits = self.prefill(tokens, cache, prompt_lens)
+            return self.decode_loop(logits, cache, max_new_tokens, temperature, top_k, eos_id, generator)
+        host = [S] * B if prompt_lens is None else torch.as_tensor(prompt_lens).reshape(B).tolist()
+        host = [min(max(int(n), 0), S) for n in host]  # read once; prefill gets the host list
+        if kv_pool is None:
+            pages = PagedKVCache.pages_needed(host, max_new_tokens, page_size)
+            cache = PagedKVCache.allocate(self.cfg, B, pages, page_size, S + max_new_tokens, dev, kv_dtype)
+        else:
+            cache = kv_pool
+            if cache.block_table.shape[0] != B or any(cache.capacity(b) for b in range(B)):
+                raise ValueError(f"generate: kv_pool must have {B} slots, all free")
+            if not pool_any_dtype and kv_dtype != cache.k.dtype:
+                raise ValueError(f"generate: kv_dtype {kv_dtype} does not agree with the pool's {cache.k.dtype}")
+        try:
+            for b, n in enumerate(host):
+                cache.reserve(b, n + max_new_tokens)
+            logits = self.prefill(tokens, cache, host)
+            return self.decode_loop(logits, cache, max_new_tokens, temperature, top_k, eos_id, generator)
+        finally:
+            if kv_pool is not None:
+                for b in range(B):
+                    cache.free(b)
+                cache.commit()
 
     @torch.no_grad()
     def decode_loop(self, logits: torch.Tensor, cache, max_new_tokens: int, temperature: float = 0.0, top_k=None,

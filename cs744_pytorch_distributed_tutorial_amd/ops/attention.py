@@ -19,6 +19,10 @@ Decoding: ``decode_attention(q, k_cache, v_cache, lens)`` is one query row per h
 An FP8 cache (``KVCache.allocate(..., dtype=torch.float8_e4m3fn)``) stores e4m3fn codes and one fp32 scale per
 (token, kv head): ``kv_cache_append`` quantises into it (``csrc/kernels/kv_append_fp8.hip``) and
 ``decode_attention(..., k_scale=, v_scale=)`` reads it.
+
+Paged cache: ``PagedKVCache`` keeps K/V in a pool of fixed-size pages shared by all sequences, with a block table
+per sequence; ``kv_cache_append_paged`` (``csrc/kernels/kv_append_paged.hip``) and ``decode_attention_paged`` (the
+paged instantiations of the decode kernel) write and read through the table, in bf16 and FP8.
 """
 from __future__ import annotations
 
@@ -301,15 +305,24 @@ def decode_attention_ref(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.
     dequantised first. The CPU path and the fallback of ``decode_attention``."""
     _no_grad_inputs("decode_attention_ref", q, k_cache, v_cache)
     fp8 = _check_cache_args("decode_attention_ref", k_cache, v_cache, k_scale, v_scale)
-    B, Hq, D = q.shape
-    Smax, Hkv = k_cache.shape[1], k_cache.shape[2]
-    rep = Hq // Hkv
+    B, D = q.shape[0], q.shape[2]
+    Smax = k_cache.shape[1]
     ct = torch.float64 if q.dtype == torch.float64 else torch.float32
     scale = 1.0 / math.sqrt(D) if scale is None else scale
     with torch.no_grad():
         if fp8:
             k_cache, v_cache = kv_dequantize(k_cache, k_scale, ct), kv_dequantize(v_cache, v_scale, ct)
         vis = torch.arange(Smax, device=q.device).view(1, Smax) < lens.to(q.device).long().clamp(0, Smax).view(B, 1)
+        return _decode_math(q, k_cache, v_cache, vis, scale, ct)
+
+
+def _decode_math(q, k_cache, v_cache, vis, scale, ct) -> torch.Tensor:
+    """softmax(q k^T * scale) v over the keys where ``vis`` bool ``[B, Smax]`` holds, in dtype ``ct``; everything
+    else is removed with ``torch.where`` from both the scores and V. -> ``[B, Hq, D]`` in q's dtype."""
+    B, Hq, D = q.shape
+    Smax, Hkv = k_cache.shape[1], k_cache.shape[2]
+    rep = Hq // Hkv
+    with torch.no_grad():
         kf = k_cache.to(ct).repeat_interleave(rep, dim=2)  # [B, Smax, Hq, D]
         vf = torch.where(vis.view(B, Smax, 1, 1), v_cache.to(ct), 0.0).repeat_interleave(rep, dim=2)
         s = torch.einsum("bhd,bshd->bhs", q.to(ct), kf) * scale
@@ -396,3 +409,401 @@ def decode_key_tile() -> int:
 def decode_splits(B: int, Hkv: int, Smax: int) -> int:
     """The key splits the kernel picks for these shapes: from B, Hkv and Smax only, never from ``lens``."""
     return native.C().decode_splits(B, Hkv, Smax)
+
+
+# ------------------------------------------------------------------ the paged KV cache
+PAGE_TILE = 64  # decode_key_tile(): a page is whole key tiles, so a tile of the decode kernel has one table entry
+
+
+def _bytes_view(t: torch.Tensor) -> torch.Tensor:
+    """FP8 tensors are indexed through their bytes (torch indexes float8 on no device reliably)"""
+    return t.view(torch.uint8) if t.dtype == FP8 else t
+
+
+def paged_gather(pages: torch.Tensor, block_table: torch.Tensor, n: Optional[int] = None) -> torch.Tensor:
+    """The logical view of a paged tensor, in plain torch on any device: ``pages`` ``[P, page, ...]``,
+    ``block_table`` integer ``[B, C]`` -> ``[B, n, ...]`` (``n`` defaults to ``C * page``), row ``i`` of sequence b
+    being row ``i % page`` of page ``block_table[b, i // page]``. Rows of an invalid page (an entry outside
+    ``[0, P)``, ``-1`` included) come back as zeros. A copy; for the references and the tests."""
+    P, page = pages.shape[0], pages.shape[1]
+    B, C = block_table.shape
+    n = C * page if n is None else n
+    if n < 0 or n > C * page:
+        raise ValueError(f"paged_gather: n {n} outside [0, {C} * {page}]")
+    cols = -(-n // page)
+    t = block_table[:, :cols].to(pages.device).long()
+    valid = (t >= 0) & (t < P)
+    src = _bytes_view(pages)
+    out = src[t.clamp(0, P - 1).reshape(-1)].reshape(B, cols, *src.shape[1:])
+    out = torch.where(valid.view(B, cols, *([1] * (src.dim() - 1))), out, torch.zeros((), dtype=src.dtype,
+                                                                                       device=src.device))
+    return out.reshape(B, cols * page, *src.shape[2:])[:, :n].view(pages.dtype)
+
+
+def _paged_visible(block_table: torch.Tensor, lens: torch.Tensor, P: int, page: int, device) -> torch.Tensor:
+    """bool [B, C * page]: key n of sequence b is visible iff n < lens[b] (clamped into [0, C * page]) and its
+    table entry lies in [0, P)"""
+    B, C = block_table.shape
+    Smax = C * page
+    t = block_table.to(device).long()
+    valid = ((t >= 0) & (t < P)).repeat_interleave(page, dim=1)
+    return valid & (torch.arange(Smax, device=device).view(1, Smax) < lens.to(device).long().clamp(0, Smax).view(B, 1))
+
+
+def _check_paged_args(name: str, k_pages, v_pages, block_table, k_scale, v_scale) -> bool:
+    """-> whether the pools are FP8; ValueError for shapes, a bad page size, or a dtype and scales that do not go
+    together"""
+    if k_pages.dim() != 4 or k_pages.shape != v_pages.shape:
+        raise ValueError(f"{name}: the pools must be [P, page, Hkv, D] of one shape")
+    page = k_pages.shape[1]
+    if page < PAGE_TILE or page % PAGE_TILE != 0:
+        raise ValueError(f"{name}: the page size must be a positive multiple of {PAGE_TILE}, got {page}")
+    if block_table.dim() != 2 or block_table.dtype.is_floating_point or block_table.dtype == torch.bool:
+        raise ValueError(f"{name}: block_table must be an integer [B, C] tensor")
+    fp8 = k_pages.dtype == FP8 or v_pages.dtype == FP8
+    if fp8:
+        if k_pages.dtype != v_pages.dtype:
+            raise ValueError(f"{name}: one pool is float8_e4m3fn and the other {v_pages.dtype}")
+        if k_scale is None or v_scale is None:
+            raise ValueError(f"{name}: float8_e4m3fn pools need k_scale and v_scale")
+        if k_scale.dtype != torch.float32 or v_scale.dtype != torch.float32:
+            raise ValueError(f"{name}: k_scale and v_scale must be fp32")
+        if k_scale.shape != k_pages.shape[:-1] or v_scale.shape != v_pages.shape[:-1]:
+            raise ValueError(f"{name}: the scales must be [P, page, Hkv] like the pools")
+    elif k_scale is not None or v_scale is not None:
+        raise ValueError(f"{name}: k_scale / v_scale go with float8_e4m3fn pools only, got {k_pages.dtype}")
+    return fp8
+
+
+def _paged_layout_ok(k_pages, v_pages, block_table, k_scale, v_scale, B: int) -> bool:
+    """the layout kv_append_paged.hip and the paged decode kernels take (check_paged_layout in the binding)"""
+    P, page, Hkv, D = k_pages.shape
+    fp8 = k_scale is not None
+    ts = (k_pages, v_pages, block_table) + ((k_scale, v_scale) if fp8 else ())
+    if not all(t.is_cuda and t.device == k_pages.device for t in ts):
+        return False
+    if k_pages.dtype != v_pages.dtype or k_pages.dtype != (FP8 if fp8 else torch.bfloat16):
+        return False
+    if k_pages.shape != v_pages.shape or P < 1 or Hkv < 1 or page < PAGE_TILE or page % PAGE_TILE != 0:
+        return False
+    if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B:
+        return False
+    C = block_table.shape[1]
+    if C < 1 or (C > 1 and block_table.stride(1) != 1) or (B > 1 and block_table.stride(0) < C):
+        return False
+    if C * page > 2 ** 31 - 1:
+        return False
+    for c in (k_pages, v_pages):
+        if c.stride()[1:] != (Hkv * D, D, 1) or (P > 1 and (c.stride(0) % 8 != 0 or c.stride(0) < page * Hkv * D)):
+            return False
+    if P > 1 and k_pages.stride(0) != v_pages.stride(0):
+        return False
+    if fp8:
+        for sc in (k_scale, v_scale):
+            if sc.dtype != torch.float32 or sc.shape != (P, page, Hkv):
+                return False
+            if sc.stride()[1:] != (Hkv, 1) or (P > 1 and sc.stride(0) < page * Hkv):
+                return False
+        if P > 1 and k_scale.stride(0) != v_scale.stride(0):
+            return False
+    return all(t.data_ptr() % 16 == 0 for t in (k_pages, v_pages))
+
+
+def decode_attention_paged_ref(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor,
+                               block_table: torch.Tensor, lens: torch.Tensor, scale: Optional[float] = None,
+                               k_scale: Optional[torch.Tensor] = None,
+                               v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Paged decode attention in plain torch: gather the pools through the table (``paged_gather``), dequantise an
+    FP8 pool, and run the math of ``decode_attention_ref`` over the keys that are below the length *and* on a
+    valid page. Whatever a stale row, an unowned page or an invalid entry's page holds cannot leak; a sequence with
+    no visible key gives zeros. The CPU path and the fallback of ``decode_attention_paged``."""
+    _no_grad_inputs("decode_attention_paged_ref", q, k_pages, v_pages)
+    fp8 = _check_paged_args("decode_attention_paged_ref", k_pages, v_pages, block_table, k_scale, v_scale)
+    P, page = k_pages.shape[0], k_pages.shape[1]
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    scale = 1.0 / math.sqrt(q.shape[-1]) if scale is None else scale
+    with torch.no_grad():
+        table = block_table.to(q.device)
+        kc, vc = paged_gather(k_pages, table), paged_gather(v_pages, table)
+        if fp8:
+            kc = kv_dequantize(kc, paged_gather(k_scale, table), ct)
+            vc = kv_dequantize(vc, paged_gather(v_scale, table), ct)
+        vis = _paged_visible(table, lens, P, page, q.device)
+        # the scores of masked keys are replaced, but a NaN row times q must not meet them on the way: zero K too
+        kc = torch.where(vis.view(*vis.shape, 1, 1), kc.to(ct), 0.0)
+        return _decode_math(q, kc, vc, vis, scale, ct)
+
+
+def decode_paged_native_ok(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
+                           lens: torch.Tensor, k_scale: Optional[torch.Tensor] = None,
+                           v_scale: Optional[torch.Tensor] = None) -> bool:
+    """Whether the paged gfx950 decode kernel takes these operands: GPU, bf16 q ``[B, Hq, D]`` contiguous, D in
+    {64, 128}, Hq / Hkv in {1, 2, 4, 8}, int32 contiguous ``lens``, pools ``[P, page, Hkv, D]`` contiguous in their
+    inner three dimensions with one page stride that is a multiple of 8, page a multiple of 64, an int32
+    ``block_table`` ``[B, C]`` on the same GPU with column stride 1, everything 16-byte aligned; the pools bf16
+    without scales, or float8_e4m3fn with fp32 scales ``[P, page, Hkv]``."""
+    if (k_scale is None) != (v_scale is None) or q.dim() != 3 or k_pages.dim() != 4:
+        return False
+    B, Hq, D = q.shape
+    if not (q.is_cuda and lens.is_cuda and lens.device == q.device and k_pages.device == q.device):
+        return False
+    if not _paged_layout_ok(k_pages, v_pages, block_table, k_scale, v_scale, B):
+        return False
+    Hkv = k_pages.shape[2]
+    if q.dtype != torch.bfloat16 or lens.dtype != torch.int32 or k_pages.shape[3] != D or D not in (64, 128):
+        return False
+    if B > 65535 or Hq % Hkv != 0 or Hq // Hkv not in (1, 2, 4, 8) or lens.shape != (B,) or not lens.is_contiguous():
+        return False
+    return q.is_contiguous() and q.data_ptr() % 16 == 0
+
+
+def decode_attention_paged(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
+                           lens: torch.Tensor, scale: Optional[float] = None, splits: Optional[int] = None,
+                           k_scale: Optional[torch.Tensor] = None,
+                           v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One query row per head against a paged KV cache: q ``[B, Hq, D]``, pools ``[P, page, Hkv, D]`` shared by all
+    sequences, ``block_table`` int32 ``[B, C]`` (``table[:, :c]`` of a wider table is fine), ``lens`` int32 ``[B]``
+    -> ``[B, Hq, D]``. Key ``n`` of sequence b is row ``n % page`` of page ``block_table[b, n // page]``; it is
+    visible iff ``n < lens[b]`` (clamped into ``[0, C * page]``) and the entry lies in ``[0, P)``. An entry outside
+    that range (``-1``: no page) masks its keys; it is never folded onto another page. Invisible rows are never
+    loaded and contribute exactly nothing; a sequence with no visible key gives zeros.
+
+    The paged instantiation of the gfx950 split-KV kernel runs when ``decode_paged_native_ok`` holds,
+    ``decode_attention_paged_ref`` otherwise. ``splits`` as in ``decode_attention``, with ``Smax = C * page``. For
+    equal ``splits`` the result has the bits of ``decode_attention`` on ``paged_gather`` of the pools. FP8 pools
+    come with ``k_scale`` / ``v_scale`` fp32 ``[P, page, Hkv]``; a dtype and scales that do not go together raise
+    ``ValueError``. Inference only."""
+    _no_grad_inputs("decode_attention_paged", q, k_pages, v_pages)
+    fp8 = _check_paged_args("decode_attention_paged", k_pages, v_pages, block_table, k_scale, v_scale)
+    if decode_paged_native_ok(q, k_pages, v_pages, block_table, lens, k_scale, v_scale):
+        scale = 1.0 / math.sqrt(q.shape[-1]) if scale is None else scale
+        nsplit = 0 if splits is None else max(int(splits), 1)
+        with torch.no_grad():
+            if fp8:
+                return native.C().attn_decode_paged_fp8(q, k_pages, v_pages, k_scale, v_scale, block_table, lens,
+                                                        float(scale), nsplit)
+            return native.C().attn_decode_paged(q, k_pages, v_pages, block_table, lens, float(scale), nsplit)
+    return decode_attention_paged_ref(q, k_pages, v_pages, block_table, lens, scale, k_scale, v_scale)
+
+
+def kv_append_paged_native_ok(k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
+                              k: torch.Tensor, v: torch.Tensor, pos: Optional[torch.Tensor] = None,
+                              counts: Optional[torch.Tensor] = None, k_scale: Optional[torch.Tensor] = None,
+                              v_scale: Optional[torch.Tensor] = None) -> bool:
+    """Whether ``kv_append_paged_kernel`` takes these operands: everything on one GPU, k / v bf16 contiguous and
+    16-byte aligned with D in {64, 128}, the pools in the layout of ``decode_paged_native_ok`` (bf16 without
+    scales, float8_e4m3fn with them), ``pos`` and ``counts`` contiguous int32 [B] on the device."""
+    if (k_scale is None) != (v_scale is None) or k.dim() != 4 or k_pages.dim() != 4:
+        return False
+    B, _, Hkv, D = k.shape
+    if not (k.is_cuda and v.is_cuda and k.device == v.device == k_pages.device):
+        return False
+    if not (k.dtype == v.dtype == torch.bfloat16 and k.is_contiguous() and v.is_contiguous() and D in (64, 128)):
+        return False
+    if not _paged_layout_ok(k_pages, v_pages, block_table, k_scale, v_scale, B):
+        return False
+    if k_pages.shape[2:] != (Hkv, D):
+        return False
+    for t in (pos, counts):
+        if t is not None and not (t.is_cuda and t.device == k.device and t.dtype == torch.int32 and t.shape == (B,)
+                                  and t.is_contiguous()):
+            return False
+    return k.data_ptr() % 16 == 0 and v.data_ptr() % 16 == 0
+
+
+def kv_cache_append_paged_ref(k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
+                              k: torch.Tensor, v: torch.Tensor, pos: Optional[torch.Tensor] = None,
+                              counts: Optional[torch.Tensor] = None, k_scale: Optional[torch.Tensor] = None,
+                              v_scale: Optional[torch.Tensor] = None) -> None:
+    """``kv_cache_append_paged`` in plain torch on any device: the store predicate per token, then index copies of
+    the stored tokens (``kv_quantize_ref`` first for an FP8 pool, a cast to the pool's dtype otherwise). The
+    boolean selection reads a count back from a GPU; the native path does not."""
+    P, page = k_pages.shape[0], k_pages.shape[1]
+    B, S, Hkv, D = k.shape
+    C = block_table.shape[1]
+    dev = k.device
+    with torch.no_grad():
+        s = torch.arange(S, device=dev).view(1, S)
+        base = torch.zeros(B, 1, dtype=torch.int64, device=dev) if pos is None else pos.to(dev).long().view(B, 1)
+        p = base + s
+        ok = (p >= 0) & (p < C * page)
+        if counts is not None:
+            ok = ok & (s < counts.to(dev).long().view(B, 1))
+        col = torch.div(p.clamp(0, C * page - 1), page, rounding_mode="floor")
+        entry = block_table.to(dev).long().gather(1, col)
+        ok = (ok & (entry >= 0) & (entry < P)).reshape(-1)
+        entry, prow = entry.reshape(-1)[ok], (p.clamp(min=0) % page).reshape(-1)[ok]
+        for x, pool, scale in ((k, k_pages, k_scale), (v, v_pages, v_scale)):
+            rows = x.reshape(B * S, Hkv, D)[ok]
+            if scale is not None:
+                codes, sc = kv_quantize_ref(rows)
+                pool.view(torch.uint8)[entry, prow] = codes.view(torch.uint8)
+                scale[entry, prow] = sc
+            else:
+                pool[entry, prow] = rows.to(pool.dtype)
+
+
+def kv_cache_append_paged(k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor, k: torch.Tensor,
+                          v: torch.Tensor, pos: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None,
+                          k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None) -> None:
+    """Store ``k`` and ``v`` ``[B, S, Hkv, D]`` into the page pools ``[P, page, Hkv, D]`` of one layer, in place,
+    through ``block_table`` int32 ``[B, C]``. Token ``(b, s)`` goes to logical position
+    ``p = (pos[b] if pos is not None else 0) + s``, row ``p % page`` of page ``block_table[b, p // page]``, and is
+    stored only if ``s < counts[b]`` (``counts`` int32 ``[B]``; absent means S), ``0 <= p < C * page`` and the
+    table entry lies in ``[0, P)``. Otherwise it is *dropped*: unlike ``kv_cache_append`` nothing is clamped, since
+    in a shared pool a folded write would land in live data. ``counts`` keeps the right-padding of a ragged prefill
+    out of the pool. Two table rows that name one page are the caller's error (unspecified there, in bounds).
+
+    FP8 pools (float8_e4m3fn with ``k_scale`` / ``v_scale`` fp32 ``[P, page, Hkv]``) take codes and scales in the
+    format of ``kv_quantize_ref``; any other pool takes the rows cast to its dtype. One launch of
+    ``kv_append_paged_kernel`` for both tensors when ``kv_append_paged_native_ok`` holds,
+    ``kv_cache_append_paged_ref`` otherwise."""
+    _no_grad_inputs("kv_cache_append_paged", k, v)
+    _check_paged_args("kv_cache_append_paged", k_pages, v_pages, block_table, k_scale, v_scale)
+    if k.dim() != 4 or k.shape != v.shape:
+        raise ValueError("kv_cache_append_paged: k, v must be [B, S, Hkv, D] of one shape")
+    B, S, Hkv, D = k.shape
+    if k_pages.shape[2:] != (Hkv, D) or block_table.shape[0] != B or block_table.shape[1] < 1:
+        raise ValueError(f"kv_cache_append_paged: pools {tuple(k_pages.shape)} and a table {tuple(block_table.shape)} "
+                         f"do not take k {tuple(k.shape)}")
+    for name, t in (("pos", pos), ("counts", counts)):
+        if t is not None and (t.shape != (B,) or t.dtype.is_floating_point):
+            raise ValueError(f"kv_cache_append_paged: {name} must be an integer [B] tensor")
+    if B == 0 or S == 0:
+        return
+    with torch.no_grad():
+        if kv_append_paged_native_ok(k_pages, v_pages, block_table, k, v, pos, counts, k_scale, v_scale):
+            native.C().kv_append_paged(k_pages, v_pages, block_table, k, v, pos, counts, k_scale, v_scale)
+            return
+    kv_cache_append_paged_ref(k_pages, v_pages, block_table, k, v, pos, counts, k_scale, v_scale)
+
+
+class PagedLayer(NamedTuple):
+    """One layer of a ``PagedKVCache`` as ``Attention.forward``'s ``kv_out``: the pools, the table, the rows'
+    token counts (a ragged prefill's lengths) and the scales of an FP8 pool."""
+    k: torch.Tensor
+    v: torch.Tensor
+    block_table: torch.Tensor
+    counts: Optional[torch.Tensor]
+    k_scale: Optional[torch.Tensor]
+    v_scale: Optional[torch.Tensor]
+
+
+class PagedKVCache:
+    """The keys and values of every layer in a pool of ``num_pages`` pages of ``page_size`` positions, shared by B
+    sequence slots: ``k``, ``v`` ``[n_layers, P, page, Hkv, hd]`` (uninitialised), ``k_scale`` / ``v_scale``
+    ``[n_layers, P, page, Hkv]`` for an FP8 pool (``None`` otherwise), one ``block_table`` int32 ``[B, Cmax]`` on the
+    device shared by all layers (``-1``: no page), ``lens`` int32 ``[B]`` on the device and ``bound``, the host
+    upper bound of ``lens``, as in ``KVCache``. Logical position n of slot b is row ``n % page`` of page
+    ``block_table[b, n // page]`` in every layer.
+
+    The allocator lives on the host: a free list and the page list of every slot (``reserve`` / ``free``), mirrored
+    in a host copy of the table that ``commit`` uploads when it has changed. ``row_bound[b]`` is the host upper
+    bound of ``lens[b]`` alone (``Llama.prefill`` sets it, ``decode_step`` advances it), which is what a slot's
+    capacity is checked against. No reference counts, no prefix sharing or copy-on-write, no scheduler."""
+
+    def __init__(self, k, v, block_table, lens, page_size: int, k_scale=None, v_scale=None):
+        self.k, self.v, self.k_scale, self.v_scale = k, v, k_scale, v_scale
+        self.block_table, self.lens, self.bound = block_table, lens, 0
+        self.page_size, self.num_pages = page_size, k.shape[1]
+        B, Cmax = block_table.shape
+        self.row_bound = [0] * B
+        self._host_table = torch.full((B, Cmax), -1, dtype=torch.int32)
+        self._rows = [[] for _ in range(B)]
+        self._free = list(range(self.num_pages - 1, -1, -1))  # a stack: page 0 is handed out first
+        self._dirty = False
+
+    @classmethod
+    def allocate(cls, cfg, B: int, num_pages: int, page_size: int = PAGE_TILE, max_len: Optional[int] = None,
+                 device=None, dtype=torch.bfloat16) -> "PagedKVCache":
+        """``cfg``: a ``LlamaConfig``; ``max_len``: the longest a sequence may grow (default ``cfg.max_seq``), which
+        sizes the table: ``Cmax = ceil(max_len / page_size)`` columns. The pools come from ``torch.empty``: no row
+        outside a sequence's length and pages is ever read as a value."""
+        if page_size < PAGE_TILE or page_size % PAGE_TILE != 0:
+            raise ValueError(f"PagedKVCache: page_size must be a positive multiple of {PAGE_TILE}, got {page_size}")
+        max_len = cfg.max_seq if max_len is None else max_len
+        if max_len < 1 or max_len > cfg.max_seq:
+            raise ValueError(f"PagedKVCache: max_len {max_len} outside [1, max_seq {cfg.max_seq}]")
+        if B < 1 or num_pages < 1:
+            raise ValueError("PagedKVCache: B and num_pages must be at least 1")
+        shape = (cfg.n_layers, num_pages, page_size, cfg.n_kv_heads, cfg.dim // cfg.n_heads)
+        scales = (None, None)
+        if dtype == FP8:
+            scales = tuple(torch.empty(shape[:-1], device=device, dtype=torch.float32) for _ in range(2))
+        table = torch.full((B, -(-max_len // page_size)), -1, dtype=torch.int32, device=device)
+        return cls(torch.empty(shape, device=device, dtype=dtype), torch.empty(shape, device=device, dtype=dtype),
+                   table, torch.zeros(B, dtype=torch.int32, device=device), page_size, *scales)
+
+    @staticmethod
+    def pages_needed(lens, extra: int, page: int = PAGE_TILE) -> int:
+        """The pages that sequences of ``lens`` tokens growing by ``extra`` tokens each take:
+        ``sum_b ceil((lens[b] + extra) / page)``. Host arithmetic, to size a pool."""
+        return sum(-(-(int(n) + extra) // page) for n in lens)
+
+    @property
+    def pages_free(self) -> int:
+        return len(self._free)
+
+    @property
+    def pages_in_use(self) -> int:
+        return self.num_pages - len(self._free)
+
+    @property
+    def max_len(self) -> int:
+        return self.block_table.shape[1] * self.page_size
+
+    def capacity(self, b: int) -> int:
+        """the positions slot b's pages hold"""
+        return len(self._rows[b]) * self.page_size
+
+    def pages_of(self, b: int) -> list:
+        return list(self._rows[b])
+
+    def reserve(self, b: int, n_tokens: int) -> None:
+        """Grow slot b to ``ceil(n_tokens / page)`` pages (never shrinks). ``RuntimeError``, with nothing changed,
+        when the free pages do not cover the request; ``ValueError`` when the table has no such column. Host only:
+        ``commit`` uploads the table."""
+        need = -(-n_tokens // self.page_size) - len(self._rows[b])
+        if need <= 0:
+            return
+        if len(self._rows[b]) + need > self._host_table.shape[1]:
+            raise ValueError(f"PagedKVCache.reserve: {n_tokens} tokens exceed the table's {self.max_len} positions")
+        if need > len(self._free):
+            raise RuntimeError(f"PagedKVCache.reserve: slot {b} needs {need} more pages, {len(self._free)} are free")
+        for _ in range(need):
+            page = self._free.pop()
+            self._host_table[b, len(self._rows[b])] = page
+            self._rows[b].append(page)
+        self._dirty = True
+
+    def free(self, b: int) -> None:
+        """Return slot b's pages to the free list; its table row becomes -1 (uploaded by ``commit``) and ``lens[b]``
+        0, by a device op without a read-back."""
+        if self._rows[b]:
+            self._free.extend(reversed(self._rows[b]))
+            self._rows[b] = []
+            self._host_table[b].fill_(-1)
+            self._dirty = True
+        self.row_bound[b] = 0
+        self.lens[b:b + 1].zero_()
+
+    def commit(self) -> None:
+        """Upload the host table when it has changed. The copy is staged through a freshly allocated pinned tensor
+        and is asynchronous: torch's pinned allocator keeps that block alive until the copy has run, so two
+        commits in a row need no host synchronisation and cannot tear."""
+        if not self._dirty:
+            return
+        if self.block_table.is_cuda:
+            stage = torch.empty(self._host_table.shape, dtype=torch.int32, pin_memory=True)
+            stage.copy_(self._host_table)
+            self.block_table.copy_(stage, non_blocking=True)
+        else:
+            self.block_table.copy_(self._host_table)
+        self._dirty = False
+
+    def layer(self, l: int, counts: Optional[torch.Tensor] = None, cols: Optional[int] = None) -> PagedLayer:
+        """layer l's pools with the first ``cols`` table columns (all by default)"""
+        table = self.block_table if cols is None else self.block_table[:, :cols]
+        fp8 = self.k_scale is not None
+        return PagedLayer(self.k[l], self.v[l], table, counts, self.k_scale[l] if fp8 else None,
+                          self.v_scale[l] if fp8 else None)

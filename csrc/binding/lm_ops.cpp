@@ -599,6 +599,179 @@ void kv_append_fp8(torch::Tensor kc, torch::Tensor vc, torch::Tensor ks, torch::
                              (size_t)sstride, cur_stream()));
 }
 
+// The layout the paged KV-cache kernels take: pools kp / vp [P, page, Hkv, D] of one shape, their inner three
+// dimensions contiguous, one page stride that holds a page and is a multiple of 8, page a positive multiple of the
+// decode key tile; where there are scales, ks / vs fp32 [P, page, Hkv], their inner two dimensions contiguous, one
+// page stride that holds a page; table int32 [B, C] on the pools' device with column stride 1 (table[:, :c] of a
+// wider table is an operand).
+struct PagedLayout {
+  int64_t P, page, Hkv, D, C, page_stride, scale_stride, table_stride;
+};
+
+PagedLayout check_paged_layout(const char* name, const torch::Tensor& kp, const torch::Tensor& vp,
+                               const torch::Tensor* ks, const torch::Tensor* vs, const torch::Tensor& table,
+                               int64_t B) {
+  TORCH_CHECK(kp.dim() == 4 && vp.dim() == 4 && kp.sizes() == vp.sizes(), name,
+              ": the pools must be [P, page, Hkv, D] of one shape");
+  const int64_t P = kp.size(0), page = kp.size(1), Hkv = kp.size(2), D = kp.size(3);
+  TORCH_CHECK(P >= 1 && Hkv >= 1, name, ": the pools need at least one page and one head");
+  const int64_t tile = cs_attn_decode_key_tile();
+  TORCH_CHECK(page >= tile && page % tile == 0, name, ": the page size must be a positive multiple of ", tile,
+              ", got ", page);
+  for (auto* t : {&kp, &vp}) {
+    TORCH_CHECK(t->stride(3) == 1 && t->stride(2) == D && t->stride(1) == Hkv * D, name,
+                ": the inner three dimensions of the pools must be contiguous");
+    TORCH_CHECK(P <= 1 || (t->stride(0) >= page * Hkv * D && t->stride(0) % 8 == 0), name,
+                ": the page stride of a pool must be a multiple of 8 and hold a page");
+  }
+  TORCH_CHECK(P <= 1 || kp.stride(0) == vp.stride(0), name, ": the pools must have one page stride");
+  TORCH_CHECK(table.is_cuda() && table.device() == kp.device(), name, ": block_table must be on the pools' device");
+  TORCH_CHECK(table.scalar_type() == at::kInt, name, ": block_table must be int32, got ", table.scalar_type());
+  TORCH_CHECK(table.dim() == 2 && table.size(0) == B && table.size(1) >= 1, name,
+              ": block_table must be [B, C] with C >= 1");
+  const int64_t C = table.size(1);
+  TORCH_CHECK(C <= 1 || table.stride(1) == 1, name, ": the column stride of block_table must be 1");
+  TORCH_CHECK(B <= 1 || table.stride(0) >= C, name, ": the row stride of block_table must hold C entries");
+  TORCH_CHECK(P <= INT_MAX && Hkv <= INT_MAX && C * page <= INT_MAX, name, ": P, Hkv or C * page too large");
+  PagedLayout L{P, page, Hkv, D, C, P > 1 ? kp.stride(0) : page * Hkv * D, 0, B > 1 ? table.stride(0) : C};
+  if (ks == nullptr) return L;
+  for (auto* t : {ks, vs}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == kp.device() && t->scalar_type() == at::kFloat, name,
+                ": the scales must be fp32 tensors on the pools' device");
+    TORCH_CHECK(t->dim() == 3 && t->size(0) == P && t->size(1) == page && t->size(2) == Hkv, name,
+                ": the scales must be [P, page, Hkv]");
+    TORCH_CHECK(t->stride(2) == 1 && t->stride(1) == Hkv, name,
+                ": the inner two dimensions of the scales must be contiguous");
+    TORCH_CHECK(P <= 1 || t->stride(0) >= page * Hkv, name, ": the page stride of a scale must hold a page");
+  }
+  TORCH_CHECK(P <= 1 || ks->stride(0) == vs->stride(0), name, ": the scales must have one page stride");
+  L.scale_stride = P > 1 ? ks->stride(0) : page * Hkv;
+  return L;
+}
+
+// decode attention against a paged KV cache (attn_decode.hip): q bf16 [B, Hq, D], pools [P, page, Hkv, D] bf16, or
+// float8_e4m3fn with scales ks / vs fp32 [P, page, Hkv] (attn_decode_paged_fp8), block_table int32 [B, C], lens
+// int32 [B] -> o like q. splits: 0 = cs_attn_decode_splits(B, Hkv, C * page); anything else is clamped into
+// [1, key tiles of C * page].
+torch::Tensor decode_paged_impl(const char* name, torch::Tensor q, torch::Tensor kp, torch::Tensor vp,
+                                const torch::Tensor* ks, const torch::Tensor* vs, torch::Tensor table,
+                                torch::Tensor lens, double scale, int64_t splits) {
+  const bool fp8 = ks != nullptr;
+  for (auto* t : {&q, &kp, &vp, &lens}) TORCH_CHECK(t->is_cuda(), name, ": all tensors must be GPU tensors");
+  for (auto* t : {&kp, &vp, &lens})
+    TORCH_CHECK(t->device() == q.device(), name, ": all tensors must be on one device");
+  if (fp8) {
+    TORCH_CHECK(q.scalar_type() == at::kBFloat16, name, ": q must be bfloat16");
+    TORCH_CHECK(kp.scalar_type() == at::kFloat8_e4m3fn && vp.scalar_type() == at::kFloat8_e4m3fn, name,
+                ": the pools must be float8_e4m3fn");
+  } else {
+    TORCH_CHECK(q.scalar_type() == at::kBFloat16 && kp.scalar_type() == at::kBFloat16 &&
+                    vp.scalar_type() == at::kBFloat16, name, ": q and the pools must be bfloat16");
+  }
+  TORCH_CHECK(q.dim() == 3, name, ": q must be [B, Hq, D]");
+  const int64_t B = q.size(0), Hq = q.size(1), D = q.size(2);
+  const PagedLayout L = check_paged_layout(name, kp, vp, ks, vs, table, B);
+  TORCH_CHECK(L.D == D, name, ": q and the pools must agree in D");
+  TORCH_CHECK(D == 64 || D == 128, name, ": head_dim must be 64 or 128, got ", D);
+  TORCH_CHECK(Hq % L.Hkv == 0 && (Hq / L.Hkv == 1 || Hq / L.Hkv == 2 || Hq / L.Hkv == 4 || Hq / L.Hkv == 8), name,
+              ": query heads per kv head must be 1, 2, 4 or 8, got Hq ", Hq, ", Hkv ", L.Hkv);
+  TORCH_CHECK(lens.scalar_type() == at::kInt, name, ": lens must be int32, got ", lens.scalar_type());
+  TORCH_CHECK(lens.dim() == 1 && lens.size(0) == B && lens.is_contiguous(), name, ": lens must be a contiguous [B]");
+  TORCH_CHECK(q.is_contiguous(), name, ": q must be contiguous");
+  TORCH_CHECK(B <= 65535 && L.Hkv <= 65535, name, ": B or Hkv too large");
+  check_aligned(q, "q"); check_aligned(kp, "k_pages"); check_aligned(vp, "v_pages");
+  DevGuard g(q.device());
+  auto o = torch::empty_like(q);
+  if (B == 0) return o;
+  const int Smax = (int)(L.C * L.page);
+  const int64_t tiles = cs_attn_decode_max_splits(Smax);
+  const int nsplit = splits == 0 ? cs_attn_decode_splits((int)B, (int)L.Hkv, Smax)
+                                 : (int)std::min<int64_t>(std::max<int64_t>(splits, 1), tiles);
+  torch::Tensor ws;
+  float* wsp = nullptr;
+  if (nsplit > 1) {
+    ws = torch::empty({(int64_t)cs_attn_decode_ws_floats((int)B, (int)Hq, (int)D, nsplit)},
+                      q.options().dtype(at::kFloat));
+    wsp = ws.data_ptr<float>();
+  }
+  check_aligned(o, "o");
+  if (fp8) {
+    CS_LAUNCH(cs_attn_decode_paged_fp8(q.data_ptr(), kp.data_ptr(), vp.data_ptr(), ks->data_ptr<float>(),
+                                       vs->data_ptr<float>(), table.data_ptr<int>(), lens.data_ptr<int>(), o.data_ptr(),
+                                       wsp, (int)B, (int)L.C, (int)Hq, (int)L.Hkv, (int)D, (int)L.P, (int)L.page,
+                                       (size_t)L.page_stride, (size_t)L.scale_stride, (size_t)L.table_stride, nsplit,
+                                       (float)scale, cur_stream()));
+    return o;
+  }
+  CS_LAUNCH(cs_attn_decode_paged(q.data_ptr(), kp.data_ptr(), vp.data_ptr(), table.data_ptr<int>(),
+                                 lens.data_ptr<int>(), o.data_ptr(), wsp, (int)B, (int)L.C, (int)Hq, (int)L.Hkv, (int)D,
+                                 (int)L.P, (int)L.page, (size_t)L.page_stride, (size_t)L.table_stride, nsplit,
+                                 (float)scale, cur_stream()));
+  return o;
+}
+
+torch::Tensor attn_decode_paged(torch::Tensor q, torch::Tensor kp, torch::Tensor vp, torch::Tensor table,
+                                torch::Tensor lens, double scale, int64_t splits) {
+  return decode_paged_impl("attn_decode_paged", q, kp, vp, nullptr, nullptr, table, lens, scale, splits);
+}
+
+torch::Tensor attn_decode_paged_fp8(torch::Tensor q, torch::Tensor kp, torch::Tensor vp, torch::Tensor ks,
+                                    torch::Tensor vs, torch::Tensor table, torch::Tensor lens, double scale,
+                                    int64_t splits) {
+  return decode_paged_impl("attn_decode_paged_fp8", q, kp, vp, &ks, &vs, table, lens, scale, splits);
+}
+
+// append to a paged KV cache (kv_append_paged.hip), in place: k / v bf16 [B, S, Hkv, D] contiguous -> the pools
+// [P, page, Hkv, D] through block_table int32 [B, C], at logical positions (pos ? pos[b] : 0) + s; a token with
+// s >= counts[b], a position outside [0, C * page) or a table entry outside [0, P) is dropped. With ks / vs the
+// pools are float8_e4m3fn and the rows are quantised (scales fp32 [P, page, Hkv]); without, the pools are bf16.
+void kv_append_paged(torch::Tensor kp, torch::Tensor vp, torch::Tensor table, torch::Tensor k, torch::Tensor v,
+                     c10::optional<torch::Tensor> pos, c10::optional<torch::Tensor> counts,
+                     c10::optional<torch::Tensor> ks, c10::optional<torch::Tensor> vs) {
+  const char* name = "kv_append_paged";
+  TORCH_CHECK(ks.has_value() == vs.has_value(), name, ": k_scale and v_scale go together");
+  const bool fp8 = ks.has_value();
+  for (auto* t : {&kp, &vp, &k, &v}) {
+    TORCH_CHECK(t->is_cuda(), name, ": all tensors must be GPU tensors");
+    TORCH_CHECK(t->device() == k.device(), name, ": all tensors must be on one device");
+  }
+  TORCH_CHECK(k.scalar_type() == at::kBFloat16 && v.scalar_type() == at::kBFloat16, name, ": k and v must be bfloat16");
+  if (fp8) {
+    TORCH_CHECK(kp.scalar_type() == at::kFloat8_e4m3fn && vp.scalar_type() == at::kFloat8_e4m3fn, name,
+                ": pools that come with scales must be float8_e4m3fn");
+  } else {
+    TORCH_CHECK(kp.scalar_type() == at::kBFloat16 && vp.scalar_type() == at::kBFloat16, name,
+                ": pools without scales must be bfloat16");
+  }
+  TORCH_CHECK(k.dim() == 4 && k.sizes() == v.sizes() && k.is_contiguous() && v.is_contiguous(), name,
+              ": k and v must be contiguous [B, S, Hkv, D] of one shape");
+  const int64_t B = k.size(0), S = k.size(1), Hkv = k.size(2), D = k.size(3);
+  TORCH_CHECK(D == 64 || D == 128, name, ": head_dim must be 64 or 128, got ", D);
+  const PagedLayout L = check_paged_layout(name, kp, vp, fp8 ? &*ks : nullptr, fp8 ? &*vs : nullptr, table, B);
+  TORCH_CHECK(L.Hkv == Hkv && L.D == D, name, ": the pools must agree with k in Hkv and D");
+  const int* ptrs[2] = {nullptr, nullptr};
+  int i = 0;
+  for (auto* t : {&pos, &counts}) {
+    if (t->has_value()) {
+      const torch::Tensor& x = **t;
+      TORCH_CHECK(x.is_cuda() && x.device() == k.device() && x.scalar_type() == at::kInt && x.dim() == 1 &&
+                      x.size(0) == B && x.is_contiguous(),
+                  name, i == 0 ? ": pos" : ": counts", " must be a contiguous int32 [B] on k's device");
+      ptrs[i] = x.data_ptr<int>();
+    }
+    ++i;
+  }
+  TORCH_CHECK(B <= INT_MAX && S <= INT_MAX, name, ": sizes too large");
+  check_aligned(k, "k"); check_aligned(v, "v"); check_aligned(kp, "k_pages"); check_aligned(vp, "v_pages");
+  if (B == 0 || S == 0) return;
+  DevGuard g(k.device());
+  CS_LAUNCH(cs_kv_append_paged(k.data_ptr(), v.data_ptr(), ptrs[0], ptrs[1], table.data_ptr<int>(), kp.data_ptr(),
+                               vp.data_ptr(), fp8 ? ks->data_ptr<float>() : nullptr,
+                               fp8 ? vs->data_ptr<float>() : nullptr, (int)B, (int)S, (int)L.C, (int)Hkv, (int)D,
+                               (int)L.P, (int)L.page, (size_t)L.page_stride, (size_t)L.scale_stride,
+                               (size_t)L.table_stride, cur_stream()));
+}
+
 // C = a @ b on the bf16 matrix cores (gemm_bf16.hip). a: [M, K], b: [K, N], bf16, each with unit
 // stride along one of its two dimensions (so x @ w.t(), dy @ w and dy.t() @ x all run without a
 // copy); out: a new bf16 (out_f32 false) or fp32 [M, N] tensor, or `acc` [M, N] += a @ b (fp32, or
@@ -736,6 +909,21 @@ void register_lm_ops(pybind11::module& m) {
         "quantise k, v bf16 [B,S,Hkv,D] into float8_e4m3fn caches and fp32 scales at pos[b] + s (clamped), in place",
         py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("k"), py::arg("v"),
         py::arg("pos") = c10::nullopt);
+  m.def("attn_decode_paged", &attn_decode_paged,
+        "decode attention through a block table: q bf16 [B,Hq,D], pools bf16 [P,page,Hkv,D], block_table int32 [B,C], "
+        "lens int32 [B] -> o [B,Hq,D]; splits 0: decode_splits(B, Hkv, C * page), otherwise clamped",
+        py::arg("q"), py::arg("k_pages"), py::arg("v_pages"), py::arg("block_table"), py::arg("lens"), py::arg("scale"),
+        py::arg("splits") = 0);
+  m.def("attn_decode_paged_fp8", &attn_decode_paged_fp8,
+        "attn_decode_paged against float8_e4m3fn pools with fp32 scales [P,page,Hkv] per (row, kv head)",
+        py::arg("q"), py::arg("k_pages"), py::arg("v_pages"), py::arg("k_scale"), py::arg("v_scale"),
+        py::arg("block_table"), py::arg("lens"), py::arg("scale"), py::arg("splits") = 0);
+  m.def("kv_append_paged", &kv_append_paged,
+        "store k, v bf16 [B,S,Hkv,D] into paged pools at pos[b] + s through block_table (dropped where s >= counts[b], "
+        "outside the table or on an invalid page), in place; with scales: float8_e4m3fn pools, quantised",
+        py::arg("k_pages"), py::arg("v_pages"), py::arg("block_table"), py::arg("k"), py::arg("v"),
+        py::arg("pos") = c10::nullopt, py::arg("counts") = c10::nullopt, py::arg("k_scale") = c10::nullopt,
+        py::arg("v_scale") = c10::nullopt);
   m.def("decode_key_tile", &cs_attn_decode_key_tile, "keys a workgroup of the decode kernel reads per trip");
   m.def("decode_splits", [](int64_t B, int64_t Hkv, int64_t Smax) {
           TORCH_CHECK(B >= 0 && Hkv >= 0 && Smax >= 0 && B <= INT_MAX && Hkv <= INT_MAX && Smax <= INT_MAX,

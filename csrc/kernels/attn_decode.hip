@@ -32,6 +32,17 @@
 //   values at a time by v_cvt_pk_f32_fp8. The key's scale multiplies the finished score, (q . k8) * ks, and the
 //   value's scale the weight, p * vs: G multiplies per key each, not D. A masked key loads neither codes nor
 //   scales. With power-of-two scales this is the arithmetic of the bf16 instantiation on the dequantised cache.
+//
+// Where key n of sequence b lives is the other compile-time property of the cache argument (kPaged).
+//   Contiguous (Bf16Cache, Fp8Cache): row n of cache[b].
+//   Paged (PagedBf16Cache: cs_attn_decode_paged, PagedFp8Cache: cs_attn_decode_paged_fp8): kc / vc are pools
+//   [P, page, Hkv, D] shared by all sequences (ks / vs [P, page, Hkv]), page a multiple of the key tile, and
+//   table int32 [B, C] names the pages of a sequence: key n is row n % page of page table[b, n / page], and
+//   Smax = C * page. A page is whole tiles, so a tile has one table entry: the workgroup reads it once per trip
+//   (it depends on blockIdx and the trip count only: a scalar load), and an entry outside [0, P) masks the
+//   tile's keys in the predicate that guards the loads, exactly like keys past the length: never loaded, score
+//   -inf. Nothing else differs, so for equal nsplit and lens the paged kernels return the bits of the
+//   contiguous ones on the gathered cache.
 #include <math.h>
 
 #include "common.h"
@@ -68,10 +79,12 @@ __device__ __forceinline__ void unpack8(const uint4& w, float (&f)[8]) {
 }
 
 // The cache formats. Row: what a lane loads of a key row, its eight elements; k / v and batch_stride count
-// elements; unpack: the eight values in fp32; kScaled: whether ks / vs [B, Smax, Hkv] hold a scale per row.
+// elements; unpack: the eight values in fp32; kScaled: whether ks / vs [B, Smax, Hkv] hold a scale per row;
+// kPaged: whether the rows are reached through a block table (PageMap below).
 struct Bf16Cache {
   using Row = uint4;
   static constexpr bool kScaled = false;
+  static constexpr bool kPaged = false;
   const __bf16 *k, *v;
   size_t batch_stride;
   static __device__ __forceinline__ void unpack(const Row& w, float (&f)[8]) { unpack8(w, f); }
@@ -80,6 +93,7 @@ struct Bf16Cache {
 struct Fp8Cache {
   using Row = uint2;
   static constexpr bool kScaled = true;
+  static constexpr bool kPaged = false;
   const unsigned char *k, *v;
   size_t batch_stride;
   const float *ks, *vs;
@@ -91,6 +105,25 @@ struct Fp8Cache {
     f[0] = a[0]; f[1] = a[1]; f[2] = b[0]; f[3] = b[1];
     f[4] = c[0]; f[5] = c[1]; f[6] = d[0]; f[7] = d[1];
   }
+};
+
+// The block table of a paged cache: table[b * row_stride + c] is the page of keys c * page .. (c + 1) * page - 1
+// of sequence b, valid when it lies in [0, pages); tiles = page / kDecKT. In the paged formats batch_stride and
+// scale_batch_stride are the strides of a page, and k / v / ks / vs the pools.
+struct PageMap {
+  const int* table;
+  size_t row_stride;
+  int pages, tiles;
+};
+
+struct PagedBf16Cache : Bf16Cache {
+  static constexpr bool kPaged = true;
+  PageMap map;
+};
+
+struct PagedFp8Cache : Fp8Cache {
+  static constexpr bool kPaged = true;
+  PageMap map;
 };
 
 // exp2(a - m) with m = -inf (nothing seen yet) read as 0: exp2(-inf - 0) = 0, never exp2(-inf + inf)
@@ -132,31 +165,56 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const __bf16* __restri
   }
 
   const size_t row = (size_t)Hkv * D;
-  const size_t head = (size_t)b * cache.batch_stride + (size_t)hkv * D + d0;
+  const size_t seq = Cache::kPaged ? 0 : b;  // a pool has no sequence axis: the page's offset is added per tile
+  const size_t head = seq * cache.batch_stride + (size_t)hkv * D + d0;
   size_t shead = 0;
-  if constexpr (Cache::kScaled) shead = (size_t)b * cache.scale_batch_stride + hkv;
+  if constexpr (Cache::kScaled) shead = seq * cache.scale_batch_stride + hkv;
+  // kPaged: tile t is tile `pt` of table column `col`; both follow t without a division per trip
+  int col = 0, pt = 0;
+  if constexpr (Cache::kPaged) {
+    col = t0 / cache.map.tiles;
+    pt = t0 - col * cache.map.tiles;
+  }
   for (int t = t0; t < t1; ++t) {
     Row kr[U], vr[U];
     float ksr[U], vsr[U];  // kScaled: the scales of the key's K and V rows, the same in all its lanes
     bool ok[U];
+    // kPaged: the tile's page, one load for the workgroup. t < ntiles, so col < C: inside the table. An entry
+    // outside [0, pages) masks the tile and is never turned into an address.
+    bool page_ok = true;
+    size_t phead = 0, pshead = 0;
+    if constexpr (Cache::kPaged) {
+      const int entry = cache.map.table[(size_t)b * cache.map.row_stride + col];
+      page_ok = entry >= 0 && entry < cache.map.pages;
+      if (page_ok) {
+        phead = head + (size_t)entry * cache.batch_stride;
+        if constexpr (Cache::kScaled) pshead = shead + (size_t)entry * cache.scale_batch_stride;
+      }
+    }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int key = t * kDecKT + u * (kDecWaves * KPW) + wave * KPW + r;
       ok[u] = key < len;
+      if constexpr (Cache::kPaged) ok[u] = ok[u] && page_ok;
       // Row(0u), not Row{}: value-initialisation makes the compiler schedule the bf16 instantiations differently,
       // measurably slower at B 64 (docs/decode_attention.md, "Shared template")
       kr[u] = Row(0u);
       vr[u] = Row(0u);
       ksr[u] = vsr[u] = 0.f;
       if (ok[u]) {  // key < len <= Smax: inside the caches and the scales; a masked key reads neither
-        const size_t off = head + (size_t)key * row;
+        // kPaged: row pt * kDecKT + (key - t * kDecKT) < page of a page in [0, pages)
+        const size_t prow = (size_t)(pt * kDecKT + u * (kDecWaves * KPW) + wave * KPW + r);
+        const size_t off = Cache::kPaged ? phead + prow * row : head + (size_t)key * row;
         kr[u] = *reinterpret_cast<const Row*>(cache.k + off);
         vr[u] = *reinterpret_cast<const Row*>(cache.v + off);
         if constexpr (Cache::kScaled) {
-          ksr[u] = cache.ks[shead + (size_t)key * Hkv];
-          vsr[u] = cache.vs[shead + (size_t)key * Hkv];
+          ksr[u] = cache.ks[Cache::kPaged ? pshead + prow * Hkv : shead + (size_t)key * Hkv];
+          vsr[u] = cache.vs[Cache::kPaged ? pshead + prow * Hkv : shead + (size_t)key * Hkv];
         }
       }
+    }
+    if constexpr (Cache::kPaged) {
+      if (++pt == cache.map.tiles) { pt = 0; ++col; }
     }
     float s[U][G];
 #pragma unroll
@@ -330,13 +388,26 @@ size_t cs_attn_decode_ws_floats(int B, int Hq, int D, int nsplit) {
 
 namespace {
 
+// whether the cache holds Smax rows per sequence (contiguous) or its pages hold `page` rows (paged)
+template <typename Cache>
+bool layout_ok(const Cache& cache, int Smax, int Hkv, int D) {
+  if constexpr (Cache::kPaged) {
+    const PageMap& m = cache.map;
+    if (m.table == nullptr || reinterpret_cast<uintptr_t>(m.table) % 4 != 0 || m.pages < 1 || m.tiles < 1) return false;
+    if (Smax % (m.tiles * kDecKT) != 0 || m.row_stride < (size_t)(Smax / (m.tiles * kDecKT))) return false;
+    return cache.batch_stride % 8 == 0 && cache.batch_stride >= (size_t)m.tiles * kDecKT * Hkv * D;
+  } else {
+    return cache.batch_stride % 8 == 0 && cache.batch_stride >= (size_t)Smax * Hkv * D;
+  }
+}
+
 template <typename Cache>
 hipError_t decode_checked(const void* q, const Cache& cache, const int* lens, void* o, float* ws, int B, int Smax,
                           int Hq, int Hkv, int D, int nsplit, float scale, hipStream_t stream) {
   if (B == 0) return hipSuccess;
   if (B < 0 || B > 65535 || Hkv < 1 || Hkv > 65535 || Hq < 1 || Hq % Hkv != 0 || Smax < 1) return hipErrorInvalidValue;
   if (nsplit < 1 || nsplit > cs_attn_decode_max_splits(Smax)) return hipErrorInvalidValue;
-  if (cache.batch_stride % 8 != 0 || cache.batch_stride < (size_t)Smax * Hkv * D) return hipErrorInvalidValue;
+  if (!layout_ok(cache, Smax, Hkv, D)) return hipErrorInvalidValue;
   if (!aligned16(q) || !aligned16(cache.k) || !aligned16(cache.v) || !aligned16(o) || lens == nullptr)
     return hipErrorInvalidValue;
   if (nsplit > 1 && !aligned16(ws)) return hipErrorInvalidValue;
@@ -365,5 +436,37 @@ hipError_t cs_attn_decode_fp8(const void* q, const void* kc, const void* vc, con
                 scale_batch_stride < (size_t)Smax * Hkv))
     return hipErrorInvalidValue;
   const Fp8Cache cache{(const unsigned char*)kc, (const unsigned char*)vc, batch_stride, ks, vs, scale_batch_stride};
+  return decode_checked(q, cache, lens, o, ws, B, Smax, Hq, Hkv, D, nsplit, scale, stream);
+}
+
+namespace {
+
+// Smax = C * page of a paged cache, or 0 when page is no positive multiple of the key tile or Smax overflows
+int paged_smax(int C, int page) {
+  if (C < 1 || page < kDecKT || page % kDecKT != 0 || (int64_t)C * page > 0x7fffffff) return 0;
+  return C * page;
+}
+
+}  // namespace
+
+hipError_t cs_attn_decode_paged(const void* q, const void* kp, const void* vp, const int* table, const int* lens,
+                                void* o, float* ws, int B, int C, int Hq, int Hkv, int D, int pages, int page,
+                                size_t page_stride, size_t table_stride, int nsplit, float scale, hipStream_t stream) {
+  const int Smax = paged_smax(C, page);
+  if (B > 0 && Smax == 0) return hipErrorInvalidValue;
+  PagedBf16Cache cache{{(const __bf16*)kp, (const __bf16*)vp, page_stride}, {table, table_stride, pages, page / kDecKT}};
+  return decode_checked(q, cache, lens, o, ws, B, Smax, Hq, Hkv, D, nsplit, scale, stream);
+}
+
+hipError_t cs_attn_decode_paged_fp8(const void* q, const void* kp, const void* vp, const float* ks, const float* vs,
+                                    const int* table, const int* lens, void* o, float* ws, int B, int C, int Hq,
+                                    int Hkv, int D, int pages, int page, size_t page_stride, size_t scale_page_stride,
+                                    size_t table_stride, int nsplit, float scale, hipStream_t stream) {
+  const int Smax = paged_smax(C, page);
+  if (B > 0 && (Smax == 0 || ks == nullptr || vs == nullptr || reinterpret_cast<uintptr_t>(ks) % 4 != 0 ||
+                reinterpret_cast<uintptr_t>(vs) % 4 != 0 || Hkv < 1 || scale_page_stride < (size_t)page * Hkv))
+    return hipErrorInvalidValue;
+  PagedFp8Cache cache{{(const unsigned char*)kp, (const unsigned char*)vp, page_stride, ks, vs, scale_page_stride},
+                      {table, table_stride, pages, page / kDecKT}};
   return decode_checked(q, cache, lens, o, ws, B, Smax, Hq, Hkv, D, nsplit, scale, stream);
 }

@@ -18,9 +18,11 @@
 // kv_append_fp8_kernel<D>: a row lies in D / 8 adjacent lanes, one 16-byte load per lane; amax over the row's
 // lanes by xor shuffles (no LDS); four v_cvt_pk_fp8_f32 and one 8-byte store per lane; lane 0 of the row
 // stores the scale. 256 / (D / 8) rows per workgroup, the k rows first, then the v rows. Plain vector stores.
+// The row arithmetic (amax, exponent, codes) is kv_quantize_row in kv_quant_device.h, shared with kv_append_paged.hip.
 #include <math.h>
 
 #include "common.h"
+#include "kv_quant_device.h"
 #include "launchers.h"
 
 namespace {
@@ -49,36 +51,13 @@ __global__ __launch_bounds__(256) void kv_append_fp8_kernel(const __bf16* __rest
   if (s + 1 < S && (p + 1 < 0 ? 0 : (p + 1 > last ? last : p + 1)) == pc) return;  // the successor lands here too
 
   const uint4 w = *reinterpret_cast<const uint4*>((is_v ? v : k) + r * D + d0);
-  float f[8];
-  f[0] = __uint_as_float(w.x << 16); f[1] = __uint_as_float(w.x & 0xffff0000u);
-  f[2] = __uint_as_float(w.y << 16); f[3] = __uint_as_float(w.y & 0xffff0000u);
-  f[4] = __uint_as_float(w.z << 16); f[5] = __uint_as_float(w.z & 0xffff0000u);
-  f[6] = __uint_as_float(w.w << 16); f[7] = __uint_as_float(w.w & 0xffff0000u);
-  float amax = 0.f;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(f[j]));
-#pragma unroll
-  for (int off = 1; off < LPK; off <<= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
-
-  int e = 0;
-  if (amax > 0.f) {
-    const unsigned bits = __float_as_uint(amax);
-    e = (int)((bits >> 23) & 0xffu) - 126 - ((bits & 0x7fffffu) <= 0x600000u ? 9 : 8);
-    e = e < -126 ? -126 : e;  // e <= 121 (Inf): both exponent fields below stay in [1, 254]
-  }
-  const float inv = __uint_as_float((unsigned)(127 - e) << 23);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) f[j] = fminf(fmaxf(f[j] * inv, -448.f), 448.f);
-  uint2 c;
-  c.x = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
-  c.x = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], (int)c.x, true);
-  c.y = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], 0, false);
-  c.y = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], (int)c.y, true);
+  int e;
+  const uint2 c = kv_quantize_row<LPK>(w, e);  // kv_quant_device.h
 
   // b < B, pc < Smax, h < Hkv: inside the cache and the scales
   const size_t slot = (size_t)pc * Hkv + h;
   *reinterpret_cast<uint2*>((is_v ? vc : kc) + (size_t)b * batch_stride + slot * D + d0) = c;
-  if (d0 == 0) (is_v ? vs : ks)[(size_t)b * scale_batch_stride + slot] = __uint_as_float((unsigned)(127 + e) << 23);
+  if (d0 == 0) (is_v ? vs : ks)[(size_t)b * scale_batch_stride + slot] = kv_scale_of(e);
 }
 
 template <int D>

@@ -446,6 +446,32 @@ hipError_t cs_attn_decode_fp8(const void* q, const void* kc, const void* vc, con
 hipError_t cs_kv_append_fp8(const void* k, const void* v, const int* pos, void* kc, void* vc, float* ks, float* vs,
                             int B, int S, int Smax, int Hkv, int D, size_t batch_stride, size_t scale_batch_stride,
                             hipStream_t stream);
+// decode attention against a paged KV cache (attn_decode.hip, the same kernel template): kp / vp are the pools
+// [P, page, Hkv, D] of one layer, bf16 (cs_attn_decode_paged) or e4m3fn codes with ks / vs fp32 [P, page, Hkv]
+// (cs_attn_decode_paged_fp8); inner three (two) dimensions contiguous, page_stride elements (% 8 == 0) and
+// scale_page_stride floats between pages. table: int32 [B, C] on the device, column stride 1, row stride
+// table_stride: key n of sequence b is row n % page of page table[b, n / page]; an entry outside [0, pages)
+// masks its keys (never loaded). page: a positive multiple of cs_attn_decode_key_tile(). Smax = C * page is the
+// logical capacity: lens is clamped into [0, Smax], 1 <= nsplit <= cs_attn_decode_max_splits(Smax). For equal
+// nsplit and lens the result has the bits of cs_attn_decode(_fp8) on the gathered cache. Everything else as
+// cs_attn_decode; hipErrorInvalidValue on anything else.
+hipError_t cs_attn_decode_paged(const void* q, const void* kp, const void* vp, const int* table, const int* lens,
+                                void* o, float* ws, int B, int C, int Hq, int Hkv, int D, int pages, int page,
+                                size_t page_stride, size_t table_stride, int nsplit, float scale, hipStream_t stream);
+hipError_t cs_attn_decode_paged_fp8(const void* q, const void* kp, const void* vp, const float* ks, const float* vs,
+                                    const int* table, const int* lens, void* o, float* ws, int B, int C, int Hq,
+                                    int Hkv, int D, int pages, int page, size_t page_stride, size_t scale_page_stride,
+                                    size_t table_stride, int nsplit, float scale, hipStream_t stream);
+// append to a paged KV cache (kv_append_paged.hip): k / v bf16 [B, S, Hkv, D] contiguous and 16-byte aligned ->
+// the pools of one layer (layouts as above), one launch for both tensors. ks == vs == null: bf16 pools, rows
+// copied; otherwise FP8 pools, rows quantised as by cs_kv_append_fp8. Token (b, s) goes to logical position
+// p = (pos ? pos[b] : 0) + s and is stored only if s < (counts ? counts[b] : S), 0 <= p < C * page and
+// table[b, p / page] lies in [0, pages); otherwise it is dropped (never clamped). pos, counts: int32 [B] on
+// the device or null. D 64 or 128. hipErrorInvalidValue on anything else.
+hipError_t cs_kv_append_paged(const void* k, const void* v, const int* pos, const int* counts, const int* table,
+                              void* kp, void* vp, float* ks, float* vs, int B, int S, int C, int Hkv, int D, int pages,
+                              int page, size_t page_stride, size_t scale_page_stride, size_t table_stride,
+                              hipStream_t stream);
 // training BatchNorm2d (+ residual add, + ReLU) on NCHW fp32 / bf16 activations (bn_nchw.hip).
 // stat: f32 [4, C] = scale, shift, mean, invstd (written by the forward, read by the backward);
 // part: f32 scratch of cs_bn_nchw_partials(N, C) floats; coef: f32 [3, C] scratch (backward).

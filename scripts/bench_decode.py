@@ -21,6 +21,11 @@ Needs a GPU: there is no CPU fallback.
                 --kv bf16 times what Attention.decode does for a bf16 cache (.to and index_copy_ for k and for
                 v), --kv fp8 the one quantising kv_cache_append that replaces them
 
+  --paged PAGE  (native and append arms) the same keys in a paged cache of PAGE positions per page: every cache is
+                cut into pages, the pages are stored in a seeded shuffled order (consecutive logical pages are not
+                adjacent in memory) and reached through a block table: ops.attention.decode_attention_paged /
+                kv_cache_append_paged. --arm append --kv bf16 --paged times the paged bf16 append kernel.
+
   python scripts/bench_decode.py --arm native --iters 50 --warmup 10
   python scripts/bench_decode.py --arm native --kv fp8
   python scripts/bench_decode.py --summary results.jsonl   # median and range over the processes, the gate
@@ -93,6 +98,7 @@ def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--arm", choices=["native", "sdpa", "append"])
     ap.add_argument("--kv", choices=["bf16", "fp8"], default="bf16", help="the cache format (native and append arms)")
+    ap.add_argument("--paged", type=int, default=0, metavar="PAGE", help="page size of a paged cache (0: contiguous)")
     ap.add_argument("--summary", metavar="JSONL", help="summarise the result lines of several processes")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
@@ -102,8 +108,10 @@ def main() -> int:
         return summary(a.summary)
     if a.arm is None:
         ap.error("--arm or --summary")
-    if a.arm == "sdpa" and a.kv != "bf16":
-        ap.error("--arm sdpa reads bf16 caches only")
+    if a.arm == "sdpa" and (a.kv != "bf16" or a.paged):
+        ap.error("--arm sdpa reads contiguous bf16 caches only")
+    if a.paged and (a.paged < 64 or a.paged % 64):
+        ap.error("--paged: a positive multiple of 64")
     import torch
     import torch.nn.functional as F
     if not torch.cuda.is_available():
@@ -126,6 +134,18 @@ def main() -> int:
         attention.kv_cache_append(*bufs, kc, vc)
         return bufs
 
+    def paged(bufs, table_out):
+        """the tensors of one cache [B, n, ...] as pools [B * n / PAGE, PAGE, ...] in a shuffled page order; the
+        block table int32 [B, n / PAGE] is written to table_out once (every cache of a shape shares it)"""
+        B, n = bufs[0].shape[:2]
+        C = n // a.paged
+        perm = torch.randperm(B * C, generator=torch.Generator().manual_seed(B * C)).to(dev)
+        if not table_out:
+            where = torch.empty(B * C, dtype=torch.int64, device=dev)
+            where[perm] = torch.arange(B * C, device=dev)  # pool[i] = page perm[i], so page j lies at where[j]
+            table_out.append(where.view(B, C).int().contiguous())
+        return tuple(t.reshape(B * C, a.paged, *t.shape[2:]).view(torch.uint8)[perm].view(t.dtype) for t in bufs)
+
     if a.arm == "append":
         n = 2048
         for B in (1, 8, 64):
@@ -138,6 +158,16 @@ def main() -> int:
                       for _ in range(copies)]
             if fp8:
                 caches = [quantised(kc, vc) for kc, vc in caches]
+            if a.paged:
+                table = []
+                caches = [paged(c, table) for c in caches]
+                table = table[0]
+                assert attention.kv_append_paged_native_ok(*caches[0][:2], table, k, v, pos, None, *caches[0][2:])
+
+                def mk(bufs):
+                    sc = dict(k_scale=bufs[2], v_scale=bufs[3]) if fp8 else {}
+                    return lambda: attention.kv_cache_append_paged(bufs[0], bufs[1], table, k, v, pos, **sc)
+            elif fp8:
                 assert attention.kv_append_native_ok(*caches[0], k, v, pos)
 
                 def mk(bufs):
@@ -154,7 +184,8 @@ def main() -> int:
                 med, lo, hi = _timed([mk(c) for c in caches], a.warmup, a.iters)
             out.append({"name": f"append_B{B}", "B": B, "us_median": round(med, 1), "us_min": round(lo, 1),
                         "us_max": round(hi, 1)})
-        print(json.dumps({"arm": a.arm, "kv": a.kv, "kv_heads": HKV, "head_dim": D, "iters": a.iters, "shapes": out}))
+        print(json.dumps({"arm": a.arm, "kv": a.kv, "paged": a.paged, "kv_heads": HKV, "head_dim": D, "iters": a.iters,
+                          "shapes": out}))
         return 0
     shapes = [(f"B{b}_L{n}", b, n, None) for b, n in UNIFORM]
     rag = torch.randint(1, RAGGED[1] + 1, (RAGGED[0],), generator=torch.Generator().manual_seed(1))
@@ -181,7 +212,16 @@ def main() -> int:
                 assert attention.decode_native_ok(q, *caches[0][:2], lens, *caches[0][2:])
             else:
                 ref = attention.decode_attention(q, *caches[0], lens, scale).float()
-        if a.arm == "native" and fp8:
+        if a.arm == "native" and a.paged:
+            table = []
+            for i in range(len(caches)):
+                caches[i] = paged(caches[i], table)
+            table = table[0]
+            assert attention.decode_paged_native_ok(q, *caches[0][:2], table, lens, *caches[0][2:])
+
+            def mk(kp, vp, ks=None, vs=None):
+                return lambda: attention.decode_attention_paged(q, kp, vp, table, lens, scale, k_scale=ks, v_scale=vs)
+        elif a.arm == "native" and fp8:
             def mk(kc, vc, ks, vs):
                 return lambda: attention.decode_attention(q, kc, vc, lens, scale, k_scale=ks, v_scale=vs)
         elif a.arm == "native":
@@ -208,7 +248,7 @@ def main() -> int:
                     "splits": native.C().decode_splits(B, HKV, n), "us_median": round(med, 1), "us_min": round(lo, 1),
                     "us_max": round(hi, 1), "kv_bytes": nbytes, "GBps": round(nbytes / med / 1e3, 1), "max_abs_diff": err})
         del caches, fns
-    print(json.dumps({"arm": a.arm, "kv": a.kv, "heads": HQ, "kv_heads": HKV, "head_dim": D, "iters": a.iters, "shapes": out}))
+    print(json.dumps({"arm": a.arm, "kv": a.kv, "paged": a.paged, "heads": HQ, "kv_heads": HKV, "head_dim": D, "iters": a.iters, "shapes": out}))
     return 0
 
 

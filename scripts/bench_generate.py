@@ -5,6 +5,7 @@ without a cache, a loop that re-runs the full forward on the growing sequence.
   --arm generate  model.generate(prompt, new) under bf16 autocast
   --arm naive     for every new token: model(tokens)[:, -1].argmax(-1), appended to tokens
   --kv fp8        (generate arm) an FP8 KV cache: model.generate(..., kv_dtype="fp8")
+  --page-size N   (generate arm) a paged KV cache of N positions per page: model.generate(..., page_size=N)
 
 llama3-1b, B 8, prompt 128, 128 new tokens by default; random weights (seeded) and a random prompt. One
 process per arm; after one untimed warm-up run, each timed run ends in a device synchronise and the median
@@ -26,13 +27,14 @@ def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--arm", choices=["generate", "naive"], required=True)
     ap.add_argument("--kv", choices=["bf16", "fp8"], default="bf16", help="the KV cache format of the generate arm")
+    ap.add_argument("--page-size", type=int, default=0, help="page size of a paged KV cache (0: the contiguous cache)")
     ap.add_argument("--model", default="llama3-1b")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--prompt", type=int, default=128)
     ap.add_argument("--new", type=int, default=128)
     ap.add_argument("--runs", type=int, default=3)
     a = ap.parse_args()
-    if a.arm == "naive" and a.kv != "bf16":
+    if a.arm == "naive" and (a.kv != "bf16" or a.page_size):
         ap.error("--arm naive has no KV cache")
     import torch
     if not torch.cuda.is_available():
@@ -48,7 +50,7 @@ def main() -> int:
     prompt = torch.randint(0, model.cfg.vocab_size, (a.batch, a.prompt), device=dev)
 
     def generate():
-        return model.generate(prompt, a.new, kv_dtype="fp8" if a.kv == "fp8" else None)
+        return model.generate(prompt, a.new, kv_dtype="fp8" if a.kv == "fp8" else None, page_size=a.page_size or None)
 
     def naive():
         tokens = prompt
@@ -68,7 +70,7 @@ def main() -> int:
             secs.append(time.perf_counter() - t0)
     assert out.shape == (a.batch, a.new)
     med = statistics.median(secs)
-    print(json.dumps({"arm": a.arm, "kv": a.kv, "model": a.model, "batch": a.batch, "prompt": a.prompt, "new": a.new,
+    print(json.dumps({"arm": a.arm, "kv": a.kv, "page_size": a.page_size, "model": a.model, "batch": a.batch, "prompt": a.prompt, "new": a.new,
                       "runs": a.runs, "s_median": round(med, 4), "s_min": round(min(secs), 4),
                       "s_max": round(max(secs), 4), "tokens_per_s": round(a.batch * a.new / med, 1),
                       "ms_per_token_step": round(med / a.new * 1e3, 3),
