@@ -22,6 +22,9 @@ inside the RMSNorm that follows it (``ops.lm.add_rms_norm``).
 Inference: ``Llama.generate`` = ``prefill`` (the training blocks, k and v copied into an ``ops.attention.KVCache``)
 plus one ``decode_step`` per token (split-KV decode attention, ``ops.attention.decode_attention``; docs/decode_attention.md).
 ``generate(..., kv_dtype="fp8")`` keeps the cache as e4m3fn codes with one fp32 scale per (token, kv head).
+``Llama.extend`` runs T > 1 new tokens per row against a filled cache (``ops.attention.extend_attention``;
+docs/extend_attention.md): a second turn on a live cache, several proposed tokens verified in one pass, and
+``prefill(..., chunk=n)`` / ``generate(..., prefill_chunk=n)``, the prompt fed n tokens at a time.
 """
 from __future__ import annotations
 
@@ -187,6 +190,36 @@ class Attention(nn.Module):
                                    k_scale=layer.k_scale, v_scale=layer.v_scale)
         return self.wo(o.reshape(B, 1, self.nh * self.hd))
 
+    def extend(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, start: torch.Tensor, counts, kc=None,
+               vc=None, slot=None, bound: int = 0, k_scale=None, v_scale=None, layer=None) -> torch.Tensor:
+        """T new tokens per row against the cache: append, then attend. ``x``: [B, T, dim]; ``cos`` / ``sin``:
+        [B * T, hd/2], the table rows of every token's own position ``start[b] + s``; ``start``: int32 [B], the
+        rows' lengths before these tokens; ``counts``: int32 [B] or None (all T), their real new tokens. Either
+        ``layer`` (an ``ops.attention.PagedLayer``: one paged append at ``start`` that drops the padding, then
+        ``extend_attention_paged``), or this layer's slab ``kc`` / ``vc`` [B, Smax, Hkv, hd] with ``bound``, a host
+        upper bound of the new lengths with ``bound <= Smax`` (the caller's check, so a padded token lands on a
+        stale position past its row's new length, never on live data): an FP8 slab comes with its scales and
+        takes one ``kv_cache_append`` at ``start``, any other one a device index copy to ``slot`` int64 [B * T]."""
+        B, T, _ = x.shape
+        # [B, T, H, hd] read as [1, B * T, H, hd]: token (b, s) is rotated by table row b * T + s
+        q, k, v = self._qkv(x.reshape(1, B * T, -1), cos, sin)
+        q, k, v = q.view(B, T, self.nh, self.hd), k.view(B, T, self.nkv, self.hd), v.view(B, T, self.nkv, self.hd)
+        from ..ops.attention import extend_attention, extend_attention_paged, kv_cache_append, kv_cache_append_paged
+        if layer is not None:
+            kv_cache_append_paged(layer.k, layer.v, layer.block_table, k, v, start, counts, k_scale=layer.k_scale,
+                                  v_scale=layer.v_scale)
+            o = extend_attention_paged(q, layer.k, layer.v, layer.block_table, start, counts, k_scale=layer.k_scale,
+                                       v_scale=layer.v_scale)
+        elif k_scale is not None:
+            kv_cache_append(kc, vc, k_scale, v_scale, k, v, start)
+            o = extend_attention(q, kc[:, :bound], vc[:, :bound], start, counts, k_scale=k_scale[:, :bound],
+                                 v_scale=v_scale[:, :bound])
+        else:
+            kc.view(-1, self.nkv, self.hd).index_copy_(0, slot, k.reshape(B * T, self.nkv, self.hd).to(kc.dtype))
+            vc.view(-1, self.nkv, self.hd).index_copy_(0, slot, v.reshape(B * T, self.nkv, self.hd).to(vc.dtype))
+            o = extend_attention(q, kc[:, :bound], vc[:, :bound], start, counts)
+        return self.wo(o.reshape(B, T, self.nh * self.hd))
+
 
 class FeedForward(nn.Module):
     def __init__(self, cfg: LlamaConfig):
@@ -300,7 +333,7 @@ class Llama(nn.Module):
         return self.tok_embeddings.weight.dtype
 
     @torch.no_grad()
-    def prefill(self, tokens: torch.Tensor, cache, prompt_lens=None, doc_ids=None) -> torch.Tensor:
+    def prefill(self, tokens: torch.Tensor, cache, prompt_lens=None, doc_ids=None, chunk=None) -> torch.Tensor:
         """Run the prompt through the model and fill ``cache`` (``ops.attention.KVCache``): the logits
         [B, V] of each row's last prompt token. ``tokens``: [B, S], right-padded; ``prompt_lens``: int [B],
         every value in [1, S] (default: all S). The blocks run with causal flash attention, which already
@@ -312,11 +345,19 @@ class Llama(nn.Module):
         read-back; none when ``prompt_lens`` is a list or a host tensor), every row's slot is grown to its own
         length and the table committed; each layer's k and v then go through the table, the first ``lens[b]``
         tokens of row b only, so the padding takes no pages. The prompt's attention runs on the fresh projections
-        as before."""
+        as before.
+
+        ``chunk=n`` feeds the prompt as ``ceil(S / n)`` ``extend`` calls of at most n tokens from an empty cache
+        (whatever ``cache`` held is forgotten), with per-row counts cut from ``prompt_lens``: the activations, the
+        attention's working set and the head's inputs scale with n, only the cache with S. The same logits and
+        the same cache contents as the one-shot call, up to summation order. For a paged cache each chunk's pages
+        are reserved and committed before the chunk runs, so the pool grows chunk by chunk."""
         if doc_ids is not None:
             raise ValueError("prefill: a document mask (doc_ids) cannot be combined with a KV cache")
         if tokens.dim() != 2:
             raise ValueError("prefill: tokens must be [B, S]")
+        if chunk is not None:
+            return self._prefill_chunked(tokens, cache, prompt_lens, int(chunk))
         from ..ops.attention import PagedKVCache
         if isinstance(cache, PagedKVCache):
             return self._prefill_paged(tokens, cache, prompt_lens)
@@ -364,6 +405,121 @@ class Llama(nn.Module):
         last = (lens.long() - 1).clamp(min=0)
         h = h[torch.arange(B, device=dev), last].unsqueeze(1)
         cache.lens, cache.bound, cache.row_bound = lens, max(host), list(host)
+        return self.output(self.norm(h)).squeeze(1)
+
+    def _prefill_chunked(self, tokens: torch.Tensor, cache, prompt_lens, chunk: int) -> torch.Tensor:
+        from ..ops.attention import PagedKVCache
+        B, S = tokens.shape
+        paged = isinstance(cache, PagedKVCache)
+        if chunk < 1:
+            raise ValueError(f"prefill: chunk must be at least 1, got {chunk}")
+        slots, room = (cache.block_table.shape[0], cache.max_len) if paged else (cache.k.shape[1], cache.k.shape[2])
+        if cache.k.shape[0] != len(self.layers) or slots != B or S < 1 or S > room:
+            raise ValueError(f"prefill: a cache of {cache.k.shape[0]} layers, {slots} sequences and {room} positions "
+                             f"does not hold {len(self.layers)} layers of [{B}, {S}] tokens")
+        dev = tokens.device
+        host = lens = None
+        if paged:  # the allocator needs the lengths on the host: read once, as in the one-shot paged prefill
+            host = [S] * B if prompt_lens is None else torch.as_tensor(prompt_lens).reshape(B).tolist()
+            host = [min(max(int(n), 0), S) for n in host]
+            cache.row_bound = [0] * B
+        elif prompt_lens is not None:
+            lens = torch.as_tensor(prompt_lens).to(device=dev, dtype=torch.int32).reshape(B).clamp(0, S)
+        cache.lens, cache.bound = torch.zeros(B, dtype=torch.int32, device=dev), 0
+        logits = None
+        for c0 in range(0, S, chunk):
+            n = min(chunk, S - c0)
+            if paged:
+                for b, m in enumerate(host):
+                    cache.reserve(b, min(m, c0 + n))
+                cache.commit()
+                counts = [min(max(m - c0, 0), n) for m in host]
+                took = torch.tensor([m > 0 for m in counts]).to(dev)
+            elif lens is None:
+                counts, took = None, None
+            else:
+                counts = (lens - c0).clamp(0, n)  # on the device: no read-back
+                took = counts > 0
+            lg = self.extend(tokens[:, c0:c0 + n], cache, counts)
+            # a row's logits are those of the last chunk that held one of its tokens
+            logits = lg if logits is None or took is None else torch.where(took.view(B, 1), lg, logits)
+        return logits
+
+    @torch.no_grad()
+    def extend(self, tokens: torch.Tensor, cache, counts=None, all_logits: bool = False) -> torch.Tensor:
+        """Run T more tokens per row on a cache that ``prefill``, ``decode_step`` or an earlier ``extend`` filled (an
+        empty one is fine): ``tokens`` [B, T] right-padded, ``counts`` int [B] the real tokens of every row (default
+        all T; clamped into [0, T]). Row b's tokens take the positions ``cache.lens[b] ..``; each layer appends their
+        k and v and runs ``ops.attention.extend_attention`` (``_paged``) over the cache. Returns the logits [B, V] of
+        each row's last real new token, or [B, T, V] with ``all_logits``. A row with ``counts[b] == 0`` keeps its
+        length; its logits are unspecified but finite.
+
+        ``cache.lens += counts`` (a device op), ``cache.bound += T``; a paged cache's ``row_bound[b]`` grows by
+        ``counts[b]`` when the counts are known on the host (``None``, a list, a host tensor: nothing is read back)
+        and by T when they are a device tensor. A contiguous cache raises ``ValueError`` when ``bound + T`` exceeds
+        its positions. A paged cache is checked per slot on the host against the pages it holds (``ValueError``
+        naming ``reserve``): nothing is allocated behind the caller's back. Packed documents have no cached form."""
+        from ..ops.attention import PagedKVCache
+        if tokens.dim() != 2 or tokens.shape[1] < 1:
+            raise ValueError("extend: tokens must be [B, T] with T >= 1")
+        B, T = tokens.shape
+        dev = tokens.device
+        paged = isinstance(cache, PagedKVCache)
+        slots = cache.block_table.shape[0] if paged else cache.k.shape[1]
+        if cache.k.shape[0] != len(self.layers) or slots != B:
+            raise ValueError(f"extend: a cache of {cache.k.shape[0]} layers and {slots} sequences does not take "
+                             f"{len(self.layers)} layers of [{B}, {T}] tokens")
+        host = cnt = None
+        if counts is None:
+            host = [T] * B
+        elif isinstance(counts, torch.Tensor) and counts.device.type != "cpu":
+            cnt = counts.to(device=dev, dtype=torch.int32).reshape(B).clamp(0, T)
+        else:
+            host = [min(max(int(n), 0), T) for n in torch.as_tensor(counts).reshape(B).tolist()]
+            cnt = torch.tensor(host, dtype=torch.int32).to(dev)
+        start = cache.lens  # int32 [B]
+        bound = cache.bound + T
+        if paged:
+            grow = host if host is not None else [T] * B
+            for b in range(B):  # host only; never allocates behind the caller's back
+                if cache.capacity(b) < cache.row_bound[b] + grow[b]:
+                    raise ValueError(f"extend: slot {b} holds {cache.capacity(b)} positions and needs "
+                                     f"{cache.row_bound[b] + grow[b]}: call cache.reserve({b}, n) and cache.commit() "
+                                     "first")
+            reach = cache.max_len
+            cols = min(-(-bound // cache.page_size), cache.block_table.shape[1])
+        else:
+            reach = cache.k.shape[2]
+            if bound > reach:
+                raise ValueError(f"extend: {cache.bound} positions in use and {T} new tokens exceed the cache's "
+                                 f"{reach} positions")
+        cos, sin = self._tables(reach, dev)
+        pos = (start.long().view(B, 1) + torch.arange(T, device=dev).view(1, T)).clamp(0, reach - 1)  # [B, T]
+        cos, sin = cos[pos.reshape(-1)], sin[pos.reshape(-1)]
+        fp8 = cache.k_scale is not None
+        slot = None
+        if not paged and not fp8:
+            slot = (torch.arange(B, device=dev).view(B, 1) * reach + pos).reshape(-1)
+        h = self.tok_embeddings(tokens)
+        for l, blk in enumerate(self.layers):
+            if paged:
+                kw = dict(layer=cache.layer(l, cols=cols))
+            elif fp8:
+                kw = dict(kc=cache.k[l], vc=cache.v[l], bound=bound, k_scale=cache.k_scale[l], v_scale=cache.v_scale[l])
+            else:
+                kw = dict(kc=cache.k[l], vc=cache.v[l], bound=bound, slot=slot)
+            h = h + blk.attention.extend(blk.attention_norm(h), cos, sin, start, cnt, **kw)
+            h = h + blk.feed_forward(blk.ffn_norm(h))
+        cache.lens = (start + T if cnt is None else start + cnt).clamp(max=reach)
+        cache.bound = bound
+        if paged:
+            cache.row_bound = [n + g for n, g in zip(cache.row_bound, grow)]
+        if all_logits:
+            return self.output(self.norm(h))
+        if cnt is None:
+            return self.output(self.norm(h[:, -1:])).squeeze(1)
+        last = (cnt.long() - 1).clamp(min=0)
+        h = h[torch.arange(B, device=dev), last].unsqueeze(1)  # [B, 1, dim], gathered on the device
         return self.output(self.norm(h)).squeeze(1)
 
     def _decode_step_paged(self, tok: torch.Tensor, cache) -> torch.Tensor:
@@ -427,7 +583,8 @@ class Llama(nn.Module):
 
     @torch.no_grad()
     def generate(self, tokens: torch.Tensor, max_new_tokens: int, prompt_lens=None, temperature: float = 0.0,
-                 top_k=None, eos_id=None, generator=None, kv_dtype=None, page_size=None, kv_pool=None) -> torch.Tensor:
+                 top_k=None, eos_id=None, generator=None, kv_dtype=None, page_size=None, kv_pool=None,
+                 prefill_chunk=None) -> torch.Tensor:
         """``int64 [B, max_new_tokens]``: the continuation of every row of ``tokens`` [B, S] (right-padded,
         ``prompt_lens`` int [B]), one ``prefill`` and then one ``decode_step`` per token. ``temperature == 0``
         is greedy argmax; otherwise a token is drawn (``torch.multinomial`` with ``generator``) from
@@ -441,7 +598,20 @@ class Llama(nn.Module):
         ``PagedKVCache`` with B slots, all free; ``len_b + max_new_tokens`` positions are reserved per row up front
         (``RuntimeError`` when the pool cannot cover them) and the rows are freed before returning, also on an
         exception; the pool's dtype is the cache's, and ``kv_dtype`` must be ``None`` or agree with it. With
-        neither argument the contiguous cache is used as before."""
+        neither argument the contiguous cache is used as before.
+
+        ``prefill_chunk=n`` feeds the prompt n tokens at a time (``prefill(..., chunk=n)``): the same tokens up to
+        summation order, with activations sized by n instead of S. Default: the one-shot prefill, as before.
+
+        Continuing a sequence (a second turn) needs the cache, so it is written with the pieces of this method::
+
+            cache = KVCache.allocate(model.cfg, B, max_len, device, model.cache_dtype(device))
+            logits = model.prefill(prompt, cache, prompt_lens)
+            answer = model.decode_loop(logits, cache, n_new)          # [B, n_new]
+            # decode_loop never feeds its last sampled token: it is not in the cache yet
+            turn = torch.cat([answer[:, -1:], next_user_tokens], 1)   # [B, 1 + T2], right-padded
+            logits = model.extend(turn, cache, counts=1 + next_lens)  # one pass over the new turn
+            answer2 = model.decode_loop(logits, cache, n_new)"""
         from ..ops.attention import KVCache, PagedKVCache
         B, S = tokens.shape
         if max_new_tokens < 0 or S + max_new_tokens > self.cfg.max_seq:
@@ -462,7 +632,7 @@ class Llama(nn.Module):
             raise ValueError("generate: pass page_size or kv_pool, not both")
         if page_size is None and kv_pool is None:
             cache = KVCache.allocate(self.cfg, B, S + max_new_tokens, dev, kv_dtype)
-            logits = self.prefill(tokens, cache, prompt_lens)
+            logits = self.prefill(tokens, cache, prompt_lens, chunk=prefill_chunk)
             return self.decode_loop(logits, cache, max_new_tokens, temperature, top_k, eos_id, generator)
         host = [S] * B if prompt_lens is None else torch.as_tensor(prompt_lens).reshape(B).tolist()
         host = [min(max(int(n), 0), S) for n in host]  # read once; prefill gets the host list
@@ -478,7 +648,7 @@ class Llama(nn.Module):
         try:
             for b, n in enumerate(host):
                 cache.reserve(b, n + max_new_tokens)
-            logits = self.prefill(tokens, cache, host)
+            logits = self.prefill(tokens, cache, host, chunk=prefill_chunk)
             return self.decode_loop(logits, cache, max_new_tokens, temperature, top_k, eos_id, generator)
         finally:
             if kv_pool is not None:
@@ -490,7 +660,12 @@ class Llama(nn.Module):
     def decode_loop(self, logits: torch.Tensor, cache, max_new_tokens: int, temperature: float = 0.0, top_k=None,
                     eos_id=None, generator=None) -> torch.Tensor:
         """The token loop of ``generate`` from the logits of a filled cache (``prefill``): pick a token, mask
-        the rows that are finished, ``decode_step``. The greedy loop reads nothing back from the device."""
+        the rows that are finished, ``decode_step``. The greedy loop reads nothing back from the device.
+
+        The last token picked is returned but not fed: the cache holds the prompt and the first
+        ``max_new_tokens - 1`` new tokens. To go on with more input, hand it to ``extend`` in front of that input:
+        ``model.extend(torch.cat([out[:, -1:], new_turn], 1), cache)`` (``generate``'s docstring has the whole
+        sequence of calls); to go on sampling alone, ``decode_loop(model.decode_step(out[:, -1], cache), cache, n)``."""
         B, dev = logits.shape[0], logits.device
         out = torch.empty(B, max_new_tokens, dtype=torch.int64, device=dev)
         finished = torch.zeros(B, dtype=torch.bool, device=dev)

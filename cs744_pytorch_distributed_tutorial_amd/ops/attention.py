@@ -23,6 +23,12 @@ An FP8 cache (``KVCache.allocate(..., dtype=torch.float8_e4m3fn)``) stores e4m3f
 Paged cache: ``PagedKVCache`` keeps K/V in a pool of fixed-size pages shared by all sequences, with a block table
 per sequence; ``kv_cache_append_paged`` (``csrc/kernels/kv_append_paged.hip``) and ``decode_attention_paged`` (the
 paged instantiations of the decode kernel) write and read through the table, in bf16 and FP8.
+
+Extend: ``extend_attention(q, k_cache, v_cache, start, counts)`` and ``extend_attention_paged`` run T new tokens per
+row against a cache that already holds their k and v behind the row's earlier keys (``csrc/kernels/attn_extend.hip``,
+the flash forward's tile loop with a bottom-right aligned causal mask; docs/extend_attention.md): continuing a
+sequence, chunked prefill, verifying several proposed tokens at once. FP8 caches are dequantised into a bf16 scratch
+first (the slow path).
 """
 from __future__ import annotations
 
@@ -807,3 +813,241 @@ class PagedKVCache:
         fp8 = self.k_scale is not None
         return PagedLayer(self.k[l], self.v[l], table, counts, self.k_scale[l] if fp8 else None,
                           self.v_scale[l] if fp8 else None)
+
+
+# ------------------------------------------------------------------ extend: T new tokens against a filled cache
+_EXT_RANGE = 0x7ffffff0  # bytes one buffer resource of the extend kernel may span (a sequence's rows / one page)
+
+
+def _extend_bounds(start: torch.Tensor, counts, B: int, T: int, Smax: int, device) -> tuple:
+    """-> (start clamped into [0, Smax], counts clamped into [0, min(T, Smax - start)]), int64 [B] on ``device``"""
+    st = start.to(device).long().clamp(0, Smax)
+    cnt = torch.full((B,), T, dtype=torch.int64, device=device) if counts is None else counts.to(device).long()
+    return st, torch.minimum(cnt.clamp(0, T), Smax - st)
+
+
+def _check_extend_args(name: str, q, B_cache: int, D_cache: int, Hkv: int, start, counts) -> None:
+    if q.dim() != 4:
+        raise ValueError(f"{name}: q must be [B, T, Hq, D]")
+    B, _, Hq, D = q.shape
+    if B_cache != B or D_cache != D or Hkv < 1 or Hq % Hkv != 0:
+        raise ValueError(f"{name}: q {tuple(q.shape)} does not go with a cache of {B_cache} sequences, {Hkv} kv heads "
+                         f"and head size {D_cache}")
+    for what, t in (("start", start), ("counts", counts)):
+        if t is not None and (t.shape != (B,) or t.dtype.is_floating_point or t.dtype == torch.bool):
+            raise ValueError(f"{name}: {what} must be an integer [B] tensor")
+    if start is None:
+        raise ValueError(f"{name}: start is required")
+
+
+def _extend_math(q, kc, vc, keyvis, st, cnt, scale, ct) -> torch.Tensor:
+    """softmax(q k^T * scale) v, query i of row b over the keys n <= st[b] + i where ``keyvis`` bool [B, Smax] holds,
+    for i < cnt[b]; in dtype ``ct``. Everything else is removed with ``torch.where`` from K, the scores and V. ->
+    ``[B, T, Hq, D]`` in q's dtype, zeros where a query sees no key."""
+    B, T, Hq, D = q.shape
+    Smax, Hkv = kc.shape[1], kc.shape[2]
+    rep = Hq // Hkv
+    dev = q.device
+    i = torch.arange(T, device=dev).view(1, T, 1)
+    n = torch.arange(Smax, device=dev).view(1, 1, Smax)
+    vis = (i < cnt.view(B, 1, 1)) & (n <= st.view(B, 1, 1) + i) & keyvis.view(B, 1, Smax)  # [B, T, Smax]
+    anyvis = vis.any(1)  # [B, Smax]: a key no query sees is removed, whatever it holds
+    kf = torch.where(anyvis.view(B, Smax, 1, 1), kc.to(ct), 0.0).repeat_interleave(rep, dim=2)
+    vf = torch.where(anyvis.view(B, Smax, 1, 1), vc.to(ct), 0.0).repeat_interleave(rep, dim=2)
+    s = torch.einsum("bthd,bshd->bhts", q.to(ct), kf) * scale
+    s = torch.where(vis.view(B, 1, T, Smax), s, float("-inf"))
+    mx = s.amax(-1, keepdim=True)
+    p = torch.exp(s - torch.where(torch.isinf(mx), 0.0, mx))
+    l = p.sum(-1, keepdim=True)
+    o = torch.einsum("bhts,bshd->bthd", p / torch.where(l > 0, l, 1.0), vf)
+    return o.to(q.dtype)
+
+
+def extend_attention_ref(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, start: torch.Tensor,
+                         counts: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+                         k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Extend attention in plain torch: q ``[B, T, Hq, D]``, the T new tokens of every row (right-padded), against
+    ``k_cache`` / ``v_cache`` ``[B, Smax, Hkv, D]`` that already hold their k and v. ``start`` integer ``[B]`` is row
+    b's length before these tokens (clamped into [0, Smax]), ``counts`` integer ``[B]`` its real new tokens (default
+    T; clamped into [0, min(T, Smax - start)]). Query ``i < counts[b]`` sees keys ``0 .. start[b] + i``; rows
+    ``i >= counts[b]`` come back as zeros. fp32 math (fp64 for fp64 inputs), GQA by head repetition; keys no query
+    sees are removed with ``torch.where`` from the scores and from V (and K), so whatever the cache holds there
+    cannot leak. FP8 caches (with ``k_scale`` / ``v_scale``) are dequantised first. The CPU path and the fallback of
+    ``extend_attention``."""
+    _no_grad_inputs("extend_attention_ref", q, k_cache, v_cache)
+    fp8 = _check_cache_args("extend_attention_ref", k_cache, v_cache, k_scale, v_scale)
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
+        raise ValueError("extend_attention_ref: the caches must be [B, Smax, Hkv, D] of one shape")
+    _check_extend_args("extend_attention_ref", q, k_cache.shape[0], k_cache.shape[3], k_cache.shape[2], start, counts)
+    B, T, _, D = q.shape
+    Smax = k_cache.shape[1]
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    with torch.no_grad():
+        if fp8:
+            k_cache, v_cache = kv_dequantize(k_cache, k_scale, ct), kv_dequantize(v_cache, v_scale, ct)
+        st, cnt = _extend_bounds(start, counts, B, T, Smax, q.device)
+        keyvis = torch.ones(B, Smax, dtype=torch.bool, device=q.device)
+        return _extend_math(q, k_cache, v_cache, keyvis, st, cnt, scale, ct)
+
+
+def extend_attention_paged_ref(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor,
+                               block_table: torch.Tensor, start: torch.Tensor, counts: Optional[torch.Tensor] = None,
+                               scale: Optional[float] = None, k_scale: Optional[torch.Tensor] = None,
+                               v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Paged extend attention in plain torch: gather the pools through the table (``paged_gather``), dequantise an
+    FP8 pool, and run the math of ``extend_attention_ref`` with ``Smax = C * page`` over the keys that are also on a
+    valid page (an entry outside ``[0, P)`` masks its keys). The CPU path and the fallback of
+    ``extend_attention_paged``."""
+    _no_grad_inputs("extend_attention_paged_ref", q, k_pages, v_pages)
+    fp8 = _check_paged_args("extend_attention_paged_ref", k_pages, v_pages, block_table, k_scale, v_scale)
+    _check_extend_args("extend_attention_paged_ref", q, block_table.shape[0], k_pages.shape[3], k_pages.shape[2],
+                       start, counts)
+    P, page = k_pages.shape[0], k_pages.shape[1]
+    B, T, _, D = q.shape
+    Smax = block_table.shape[1] * page
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    with torch.no_grad():
+        table = block_table.to(q.device)
+        kc, vc = paged_gather(k_pages, table), paged_gather(v_pages, table)
+        if fp8:
+            kc = kv_dequantize(kc, paged_gather(k_scale, table), ct)
+            vc = kv_dequantize(vc, paged_gather(v_scale, table), ct)
+        st, cnt = _extend_bounds(start, counts, B, T, Smax, q.device)
+        keyvis = ((table.long() >= 0) & (table.long() < P)).repeat_interleave(page, dim=1)
+        return _extend_math(q, kc, vc, keyvis, st, cnt, scale, ct)
+
+
+def _extend_index_ok(q: torch.Tensor, start: torch.Tensor, counts: Optional[torch.Tensor]) -> bool:
+    for t in (start, counts):
+        if t is not None and not (t.is_cuda and t.device == q.device and t.dtype == torch.int32
+                                  and t.shape == (q.shape[0],) and t.is_contiguous()):
+            return False
+    return True
+
+
+def extend_native_ok(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, start: torch.Tensor,
+                     counts: Optional[torch.Tensor] = None, k_scale: Optional[torch.Tensor] = None,
+                     v_scale: Optional[torch.Tensor] = None) -> bool:
+    """Whether ``attn_extend_kernel`` takes these operands: GPU, bf16 q ``[B, T, Hq, D]`` contiguous, D in {64, 128},
+    any Hq % Hkv == 0, bf16 caches without scales in the layout of ``decode_native_ok`` (contiguous in their inner
+    three dimensions, one batch stride that is a multiple of 8: ``cache[:, :n]`` is fine) with one sequence's rows
+    within 2 GiB, ``start`` (and ``counts``) contiguous int32 [B] on the device, everything 16-byte aligned. FP8
+    caches are not the kernel's: ``extend_attention`` dequantises them first."""
+    if k_scale is not None or v_scale is not None:
+        return False
+    if not (q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and k_cache.device == v_cache.device == q.device):
+        return False
+    if not (q.dtype == k_cache.dtype == v_cache.dtype == torch.bfloat16):
+        return False
+    if q.dim() != 4 or k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
+        return False
+    B, T, Hq, D = q.shape
+    Smax, Hkv = k_cache.shape[1], k_cache.shape[2]
+    if k_cache.shape[0] != B or k_cache.shape[3] != D or D not in (64, 128) or Smax < 1 or B > 65535 or Hq > 65535:
+        return False
+    if Hkv < 1 or Hq < 1 or Hq % Hkv != 0 or T > 2 ** 31 - 1 or not _extend_index_ok(q, start, counts):
+        return False
+    if (Smax - 1) * Hkv * D * 2 + 2 * D > _EXT_RANGE:
+        return False
+    for c in (k_cache, v_cache):
+        if c.stride()[1:] != (Hkv * D, D, 1) or (B > 1 and (c.stride(0) % 8 != 0 or c.stride(0) < Smax * Hkv * D)):
+            return False
+    if B > 1 and k_cache.stride(0) != v_cache.stride(0):
+        return False
+    return q.is_contiguous() and all(t.data_ptr() % 16 == 0 for t in (q, k_cache, v_cache))
+
+
+def extend_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, start: torch.Tensor,
+                     counts: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+                     k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """T new tokens per row against a KV cache that already holds their k and v (append, then attend): q
+    ``[B, T, Hq, D]`` right-padded, caches ``[B, Smax, Hkv, D]`` (a ``[:, :n]`` slice of a longer cache is fine),
+    ``start`` int32 ``[B]`` the rows' lengths before these tokens, ``counts`` int32 ``[B]`` their real new tokens
+    (default T) -> ``[B, T, Hq, D]``. ``start`` is clamped into [0, Smax] and ``counts`` into
+    [0, min(T, Smax - start)]. Query ``i < counts[b]`` sits at position ``start[b] + i`` and sees keys
+    ``0 .. start[b] + i`` (the bottom-right aligned causal mask); rows ``i >= counts[b]`` are zeros. Keys at or past
+    ``start[b] + counts[b]`` are stale: they are never loaded and contribute exactly nothing, V included.
+
+    The gfx950 kernel (``csrc/kernels/attn_extend.hip``, the flash forward's tile loop against the cache;
+    docs/extend_attention.md) runs when ``extend_native_ok`` holds, ``extend_attention_ref`` otherwise. T = 1 works,
+    but ``decode_attention`` is the kernel for it. FP8 caches (float8_e4m3fn with ``k_scale`` / ``v_scale``) take
+    the slow path: the operand is dequantised into a bf16 scratch (``kv_dequantize``) and the bf16 kernel runs on
+    that; a dtype and scales that do not go together raise ``ValueError``. Inference only."""
+    _no_grad_inputs("extend_attention", q, k_cache, v_cache)
+    fp8 = _check_cache_args("extend_attention", k_cache, v_cache, k_scale, v_scale)
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
+        raise ValueError("extend_attention: the caches must be [B, Smax, Hkv, D] of one shape")
+    _check_extend_args("extend_attention", q, k_cache.shape[0], k_cache.shape[3], k_cache.shape[2], start, counts)
+    if fp8 and q.is_cuda and q.dtype == torch.bfloat16 and k_cache.device == q.device:
+        with torch.no_grad():  # the slow path: a bf16 copy of the operand (stale rows may hold anything: never loaded)
+            kd = kv_dequantize(k_cache, k_scale, torch.bfloat16)
+            vd = kv_dequantize(v_cache, v_scale, torch.bfloat16)
+        if extend_native_ok(q, kd, vd, start, counts):
+            return extend_attention(q, kd, vd, start, counts, scale)
+    if extend_native_ok(q, k_cache, v_cache, start, counts, k_scale, v_scale):
+        scale = 1.0 / math.sqrt(q.shape[-1]) if scale is None else scale
+        with torch.no_grad():
+            return native.C().attn_extend(q, k_cache, v_cache, start, float(scale), counts)
+    return extend_attention_ref(q, k_cache, v_cache, start, counts, scale, k_scale, v_scale)
+
+
+def extend_paged_native_ok(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
+                           start: torch.Tensor, counts: Optional[torch.Tensor] = None,
+                           k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None) -> bool:
+    """Whether the paged ``attn_extend_kernel`` takes these operands: GPU, bf16 q ``[B, T, Hq, D]`` contiguous, D in
+    {64, 128}, any Hq % Hkv == 0, bf16 pools without scales and an int32 ``block_table`` in the layout of
+    ``decode_paged_native_ok``, one page within 2 GiB, ``start`` (and ``counts``) contiguous int32 [B] on the device,
+    everything 16-byte aligned."""
+    if k_scale is not None or v_scale is not None or q.dim() != 4 or k_pages.dim() != 4:
+        return False
+    B, T, Hq, D = q.shape
+    if not (q.is_cuda and k_pages.device == q.device):
+        return False
+    if not _paged_layout_ok(k_pages, v_pages, block_table, None, None, B):
+        return False
+    page, Hkv = k_pages.shape[1], k_pages.shape[2]
+    if q.dtype != torch.bfloat16 or k_pages.shape[3] != D or D not in (64, 128):
+        return False
+    if B > 65535 or Hq > 65535 or Hq < 1 or Hq % Hkv != 0 or T > 2 ** 31 - 1 or not _extend_index_ok(q, start, counts):
+        return False
+    if (page - 1) * Hkv * D * 2 + 2 * D > _EXT_RANGE:
+        return False
+    return q.is_contiguous() and q.data_ptr() % 16 == 0
+
+
+def extend_attention_paged(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
+                           start: torch.Tensor, counts: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+                           k_scale: Optional[torch.Tensor] = None,
+                           v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``extend_attention`` against a paged KV cache: pools ``[P, page, Hkv, D]``, ``block_table`` int32 ``[B, C]``
+    (``table[:, :c]`` of a wider table is fine), ``Smax = C * page``. Key ``n`` of sequence b is row ``n % page`` of
+    page ``block_table[b, n // page]``; an entry outside ``[0, P)`` masks its keys and is never turned into an
+    address. A 64-key tile of the kernel has one table entry, read once per tile. For equal operands the result has
+    the bits of ``extend_attention`` on ``paged_gather`` of the pools.
+
+    The paged gfx950 kernel runs when ``extend_paged_native_ok`` holds, ``extend_attention_paged_ref`` otherwise. FP8
+    pools take the slow path: the pages the table names are gathered and dequantised into a bf16 scratch
+    (``paged_gather``, ``kv_dequantize``), which the kernel reads as a pool of its own through a table that keeps
+    the invalid entries invalid. Inference only."""
+    _no_grad_inputs("extend_attention_paged", q, k_pages, v_pages)
+    fp8 = _check_paged_args("extend_attention_paged", k_pages, v_pages, block_table, k_scale, v_scale)
+    _check_extend_args("extend_attention_paged", q, block_table.shape[0], k_pages.shape[3], k_pages.shape[2], start,
+                       counts)
+    if fp8 and q.is_cuda and q.dtype == torch.bfloat16 and k_pages.device == q.device and block_table.is_cuda:
+        P, page = k_pages.shape[0], k_pages.shape[1]
+        B, C = block_table.shape
+        with torch.no_grad():  # the slow path: row b's pages become pages b * C .. b * C + C - 1 of a bf16 scratch
+            kd = kv_dequantize(paged_gather(k_pages, block_table), paged_gather(k_scale, block_table), torch.bfloat16)
+            vd = kv_dequantize(paged_gather(v_pages, block_table), paged_gather(v_scale, block_table), torch.bfloat16)
+            kd, vd = kd.view(B * C, page, *kd.shape[2:]), vd.view(B * C, page, *vd.shape[2:])
+            own = torch.arange(B * C, dtype=torch.int32, device=q.device).view(B, C)
+            table = torch.where((block_table >= 0) & (block_table < P), own, own.new_full((), -1))
+        if extend_paged_native_ok(q, kd, vd, table, start, counts):
+            return extend_attention_paged(q, kd, vd, table, start, counts, scale)
+    if extend_paged_native_ok(q, k_pages, v_pages, block_table, start, counts, k_scale, v_scale):
+        scale = 1.0 / math.sqrt(q.shape[-1]) if scale is None else scale
+        with torch.no_grad():
+            return native.C().attn_extend_paged(q, k_pages, v_pages, block_table, start, float(scale), counts)
+    return extend_attention_paged_ref(q, k_pages, v_pages, block_table, start, counts, scale, k_scale, v_scale)

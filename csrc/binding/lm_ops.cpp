@@ -772,6 +772,82 @@ void kv_append_paged(torch::Tensor kp, torch::Tensor vp, torch::Tensor table, to
                                (size_t)L.table_stride, cur_stream()));
 }
 
+// start / counts of the extend kernels: a contiguous int32 [B] on q's device (counts may be absent)
+const int* extend_index(const char* name, const char* what, const c10::optional<torch::Tensor>& t,
+                        const torch::Tensor& q, int64_t B) {
+  if (!t.has_value()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->device() == q.device() && t->scalar_type() == at::kInt && t->dim() == 1 &&
+                  t->size(0) == B && t->is_contiguous(),
+              name, ": ", what, " must be a contiguous int32 [B] on q's device");
+  return t->data_ptr<int>();
+}
+
+// extend attention (attn_extend.hip): q bf16 [B, T, Hq, D] contiguous, the T new tokens of every row, against
+// caches bf16 [B, Smax, Hkv, D] (layout as for attn_decode) that already hold their k and v; start int32 [B] the
+// rows' lengths before these tokens, counts int32 [B] (absent: T) their real new tokens -> o like q.
+torch::Tensor attn_extend(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, torch::Tensor start, double scale,
+                          c10::optional<torch::Tensor> counts) {
+  const char* name = "attn_extend";
+  for (auto* t : {&q, &kc, &vc}) {
+    TORCH_CHECK(t->is_cuda(), name, ": all tensors must be GPU tensors");
+    TORCH_CHECK(t->device() == q.device(), name, ": all tensors must be on one device");
+    TORCH_CHECK(t->scalar_type() == at::kBFloat16, name, ": q and the caches must be bfloat16");
+  }
+  TORCH_CHECK(q.dim() == 4 && q.is_contiguous(), name, ": q must be a contiguous [B, T, Hq, D]");
+  TORCH_CHECK(kc.dim() == 4 && vc.dim() == 4 && kc.sizes() == vc.sizes(), name,
+              ": the caches must be [B, Smax, Hkv, D] of one shape");
+  const int64_t B = q.size(0), T = q.size(1), Hq = q.size(2), D = q.size(3), Smax = kc.size(1), Hkv = kc.size(2);
+  TORCH_CHECK(kc.size(0) == B && kc.size(3) == D, name, ": q and the caches must agree in B and D");
+  TORCH_CHECK(D == 64 || D == 128, name, ": head_dim must be 64 or 128, got ", D);
+  TORCH_CHECK(Hkv > 0 && Hq > 0 && Hq % Hkv == 0, name, ": Hq must be a multiple of Hkv, got Hq ", Hq, ", Hkv ", Hkv);
+  TORCH_CHECK(Smax >= 1, name, ": the caches need at least one position");
+  const int* startp = extend_index(name, "start", start, q, B);
+  const int* countp = extend_index(name, "counts", counts, q, B);
+  const auto [bstride, sstride] = check_kv_layout(name, kc, vc, nullptr, nullptr);
+  (void)sstride;
+  TORCH_CHECK(B <= 65535 && Hq <= 65535 && T <= INT_MAX && Smax <= INT_MAX, name, ": B, Hq, T or Smax too large");
+  TORCH_CHECK((Smax - 1) * Hkv * D * 2 + 2 * D <= 0x7ffffff0, name, ": one sequence of the cache must lie within 2 GiB");
+  check_aligned(q, "q"); check_aligned(kc, "k_cache"); check_aligned(vc, "v_cache");
+  DevGuard g(q.device());
+  auto o = torch::empty_like(q);
+  if (B == 0 || T == 0) return o;
+  check_aligned(o, "o");
+  CS_LAUNCH(cs_attn_extend(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), startp, countp, o.data_ptr(), (int)B, (int)T,
+                           (int)Smax, (int)Hq, (int)Hkv, (int)D, (size_t)bstride, (float)scale, cur_stream()));
+  return o;
+}
+
+// the same against bf16 pools [P, page, Hkv, D] through block_table int32 [B, C] (layout as for attn_decode_paged)
+torch::Tensor attn_extend_paged(torch::Tensor q, torch::Tensor kp, torch::Tensor vp, torch::Tensor table,
+                                torch::Tensor start, double scale, c10::optional<torch::Tensor> counts) {
+  const char* name = "attn_extend_paged";
+  for (auto* t : {&q, &kp, &vp}) {
+    TORCH_CHECK(t->is_cuda(), name, ": all tensors must be GPU tensors");
+    TORCH_CHECK(t->device() == q.device(), name, ": all tensors must be on one device");
+    TORCH_CHECK(t->scalar_type() == at::kBFloat16, name, ": q and the pools must be bfloat16");
+  }
+  TORCH_CHECK(q.dim() == 4 && q.is_contiguous(), name, ": q must be a contiguous [B, T, Hq, D]");
+  const int64_t B = q.size(0), T = q.size(1), Hq = q.size(2), D = q.size(3);
+  const PagedLayout L = check_paged_layout(name, kp, vp, nullptr, nullptr, table, B);
+  TORCH_CHECK(L.D == D, name, ": q and the pools must agree in D");
+  TORCH_CHECK(D == 64 || D == 128, name, ": head_dim must be 64 or 128, got ", D);
+  TORCH_CHECK(Hq > 0 && Hq % L.Hkv == 0, name, ": Hq must be a multiple of Hkv, got Hq ", Hq, ", Hkv ", L.Hkv);
+  const int* startp = extend_index(name, "start", start, q, B);
+  const int* countp = extend_index(name, "counts", counts, q, B);
+  TORCH_CHECK(B <= 65535 && Hq <= 65535 && T <= INT_MAX, name, ": B, Hq or T too large");
+  TORCH_CHECK((L.page - 1) * L.Hkv * D * 2 + 2 * D <= 0x7ffffff0, name, ": one page of the pools must lie within 2 GiB");
+  check_aligned(q, "q"); check_aligned(kp, "k_pages"); check_aligned(vp, "v_pages");
+  DevGuard g(q.device());
+  auto o = torch::empty_like(q);
+  if (B == 0 || T == 0) return o;
+  check_aligned(o, "o");
+  CS_LAUNCH(cs_attn_extend_paged(q.data_ptr(), kp.data_ptr(), vp.data_ptr(), table.data_ptr<int>(), startp, countp,
+                                 o.data_ptr(), (int)B, (int)T, (int)L.C, (int)Hq, (int)L.Hkv, (int)D, (int)L.P,
+                                 (int)L.page, (size_t)L.page_stride, (size_t)L.table_stride, (float)scale,
+                                 cur_stream()));
+  return o;
+}
+
 // C = a @ b on the bf16 matrix cores (gemm_bf16.hip). a: [M, K], b: [K, N], bf16, each with unit
 // stride along one of its two dimensions (so x @ w.t(), dy @ w and dy.t() @ x all run without a
 // copy); out: a new bf16 (out_f32 false) or fp32 [M, N] tensor, or `acc` [M, N] += a @ b (fp32, or
@@ -924,6 +1000,15 @@ void register_lm_ops(pybind11::module& m) {
         py::arg("k_pages"), py::arg("v_pages"), py::arg("block_table"), py::arg("k"), py::arg("v"),
         py::arg("pos") = c10::nullopt, py::arg("counts") = c10::nullopt, py::arg("k_scale") = c10::nullopt,
         py::arg("v_scale") = c10::nullopt);
+  m.def("attn_extend", &attn_extend,
+        "extend attention: q bf16 [B,T,Hq,D], the T new tokens of every row, against caches bf16 [B,Smax,Hkv,D] that "
+        "already hold their k and v; query i < counts[b] sees keys 0 .. start[b] + i, padded rows give zeros",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("start"), py::arg("scale"),
+        py::arg("counts") = c10::nullopt);
+  m.def("attn_extend_paged", &attn_extend_paged,
+        "attn_extend against bf16 pools [P,page,Hkv,D] through block_table int32 [B,C]; an entry outside [0,P) masks "
+        "its keys", py::arg("q"), py::arg("k_pages"), py::arg("v_pages"), py::arg("block_table"), py::arg("start"),
+        py::arg("scale"), py::arg("counts") = c10::nullopt);
   m.def("decode_key_tile", &cs_attn_decode_key_tile, "keys a workgroup of the decode kernel reads per trip");
   m.def("decode_splits", [](int64_t B, int64_t Hkv, int64_t Smax) {
           TORCH_CHECK(B >= 0 && Hkv >= 0 && Smax >= 0 && B <= INT_MAX && Hkv <= INT_MAX && Smax <= INT_MAX,

@@ -472,6 +472,24 @@ hipError_t cs_kv_append_paged(const void* k, const void* v, const int* pos, cons
                               void* kp, void* vp, float* ks, float* vs, int B, int S, int C, int Hkv, int D, int pages,
                               int page, size_t page_stride, size_t scale_page_stride, size_t table_stride,
                               hipStream_t stream);
+// extend attention (attn_extend.hip): T new tokens per sequence against a cache that already holds their k and v.
+// q / o: bf16 [B, T, Hq, D] contiguous, right-padded; start: int32 [B] on the device, row b's length before these
+// tokens, clamped into [0, Smax] in the kernel; counts: int32 [B] or null (= T), the real new tokens of row b,
+// clamped into [0, min(T, Smax - start)]. Query i < counts[b] sees keys 0 .. start[b] + i; rows i >= counts[b] of o
+// are zeros; keys at or past start[b] + counts[b] are never loaded. kc / vc: bf16 [B, Smax, Hkv, D] as for
+// cs_attn_decode (batch_stride % 8 == 0). D 64 or 128, any Hq % Hkv == 0, all pointers 16-byte aligned, one
+// sequence's rows within 2 GiB. One flash-forward style kernel, no split over the keys: the same bits every run.
+// hipErrorInvalidValue on anything else, without a launch.
+hipError_t cs_attn_extend(const void* q, const void* kc, const void* vc, const int* start, const int* counts, void* o,
+                          int B, int T, int Smax, int Hq, int Hkv, int D, size_t batch_stride, float scale,
+                          hipStream_t stream);
+// the same against bf16 pools [P, page, Hkv, D] through table int32 [B, C] (layouts as for cs_attn_decode_paged,
+// Smax = C * page, page a positive multiple of 64): one table entry per 64-key tile, an entry outside [0, pages)
+// masks its tile and is never turned into an address. For equal operands the result has the bits of cs_attn_extend
+// on the gathered cache.
+hipError_t cs_attn_extend_paged(const void* q, const void* kp, const void* vp, const int* table, const int* start,
+                                const int* counts, void* o, int B, int T, int C, int Hq, int Hkv, int D, int pages,
+                                int page, size_t page_stride, size_t table_stride, float scale, hipStream_t stream);
 // training BatchNorm2d (+ residual add, + ReLU) on NCHW fp32 / bf16 activations (bn_nchw.hip).
 // stat: f32 [4, C] = scale, shift, mean, invstd (written by the forward, read by the backward);
 // part: f32 scratch of cs_bn_nchw_partials(N, C) floats; coef: f32 [3, C] scratch (backward).
