@@ -584,12 +584,20 @@ class Llama(nn.Module):
     @torch.no_grad()
     def generate(self, tokens: torch.Tensor, max_new_tokens: int, prompt_lens=None, temperature: float = 0.0,
                  top_k=None, eos_id=None, generator=None, kv_dtype=None, page_size=None, kv_pool=None,
-                 prefill_chunk=None) -> torch.Tensor:
+                 prefill_chunk=None, top_p=None, min_p=None, sampler=None) -> torch.Tensor:
         """``int64 [B, max_new_tokens]``: the continuation of every row of ``tokens`` [B, S] (right-padded,
         ``prompt_lens`` int [B]), one ``prefill`` and then one ``decode_step`` per token. ``temperature == 0``
         is greedy argmax; otherwise a token is drawn (``torch.multinomial`` with ``generator``) from
         ``softmax(logits / temperature)``, restricted to the ``top_k`` largest logits when given. A row that
         has emitted ``eos_id`` keeps emitting it (a device-side mask: no early exit, no synchronisation).
+
+        ``top_p`` (nucleus, 0 < p <= 1), ``min_p`` (0 <= p <= 1), a tensor [B] as ``temperature`` or ``top_k`` (per-row
+        settings; a row at temperature 0 is greedy) or ``sampler="fused"`` select the fused sampler instead:
+        ``ops.lm.sample_logits``, one launch per step on the GPU. Its filters run top-k, min-p, top-p in that order;
+        tokens tied at the k-th value or at the nucleus cut are all kept; the token is drawn by inverse CDF in
+        vocabulary order at one ``u = torch.rand(B, generator=generator)`` per step, so ``generator`` (on the tokens'
+        device) fixes the tokens, though not to the ones ``torch.multinomial`` would give for the same seed. With none
+        of these arguments the path is the one above, unchanged.
         ``kv_dtype``: the cache's dtype; ``None`` is ``cache_dtype``, ``"fp8"`` or ``torch.float8_e4m3fn`` an FP8
         cache (e4m3fn codes and one fp32 scale per token and kv head: about half the bytes of bf16).
 
@@ -616,7 +624,8 @@ class Llama(nn.Module):
         B, S = tokens.shape
         if max_new_tokens < 0 or S + max_new_tokens > self.cfg.max_seq:
             raise ValueError(f"generate: {S} prompt + {max_new_tokens} new tokens exceed max_seq {self.cfg.max_seq}")
-        if temperature < 0 or (top_k is not None and top_k < 1):
+        if (not isinstance(temperature, torch.Tensor) and temperature < 0) or (
+                top_k is not None and not isinstance(top_k, torch.Tensor) and top_k < 1):
             raise ValueError("generate: temperature must be >= 0 and top_k >= 1")
         dev = tokens.device
         if max_new_tokens == 0:
@@ -633,7 +642,8 @@ class Llama(nn.Module):
         if page_size is None and kv_pool is None:
             cache = KVCache.allocate(self.cfg, B, S + max_new_tokens, dev, kv_dtype)
             logits = self.prefill(tokens, cache, prompt_lens, chunk=prefill_chunk)
-            return self.decode_loop(logits, cache, max_new_tokens, temperature, top_k, eos_id, generator)
+            return self.decode_loop(logits, cache, max_new_tokens, temperature, top_k, eos_id, generator, top_p, min_p,
+                                    sampler)
         host = [S] * B if prompt_lens is None else torch.as_tensor(prompt_lens).reshape(B).tolist()
         host = [min(max(int(n), 0), S) for n in host]  # read once; prefill gets the host list
         if kv_pool is None:
@@ -649,7 +659,8 @@ class Llama(nn.Module):
             for b, n in enumerate(host):
                 cache.reserve(b, n + max_new_tokens)
             logits = self.prefill(tokens, cache, host, chunk=prefill_chunk)
-            return self.decode_loop(logits, cache, max_new_tokens, temperature, top_k, eos_id, generator)
+            return self.decode_loop(logits, cache, max_new_tokens, temperature, top_k, eos_id, generator, top_p, min_p,
+                                    sampler)
         finally:
             if kv_pool is not None:
                 for b in range(B):
@@ -658,16 +669,43 @@ class Llama(nn.Module):
 
     @torch.no_grad()
     def decode_loop(self, logits: torch.Tensor, cache, max_new_tokens: int, temperature: float = 0.0, top_k=None,
-                    eos_id=None, generator=None) -> torch.Tensor:
+                    eos_id=None, generator=None, top_p=None, min_p=None, sampler=None) -> torch.Tensor:
         """The token loop of ``generate`` from the logits of a filled cache (``prefill``): pick a token, mask
         the rows that are finished, ``decode_step``. The greedy loop reads nothing back from the device.
 
         The last token picked is returned but not fed: the cache holds the prompt and the first
         ``max_new_tokens - 1`` new tokens. To go on with more input, hand it to ``extend`` in front of that input:
         ``model.extend(torch.cat([out[:, -1:], new_turn], 1), cache)`` (``generate``'s docstring has the whole
-        sequence of calls); to go on sampling alone, ``decode_loop(model.decode_step(out[:, -1], cache), cache, n)``."""
+        sequence of calls); to go on sampling alone, ``decode_loop(model.decode_step(out[:, -1], cache), cache, n)``.
+
+        ``top_p``, ``min_p``, a tensor [B] as ``temperature`` or ``top_k``, or ``sampler="fused"`` run the fused
+        sampler (``generate`` has the rules: ties at the k-th value and at the nucleus cut are kept, and the draw's
+        ``u`` comes from ``generator``): per step one ``torch.rand(B)`` and one ``sample_logits`` call, which also
+        applies the eos mask; nothing is read back. Without them the loop below is the one there has always been."""
         B, dev = logits.shape[0], logits.device
         out = torch.empty(B, max_new_tokens, dtype=torch.int64, device=dev)
+        if sampler not in (None, "fused"):
+            raise ValueError(f"decode_loop: sampler must be None or 'fused', got {sampler!r}")
+        if (sampler == "fused" or top_p is not None or min_p is not None or isinstance(temperature, torch.Tensor)
+                or isinstance(top_k, torch.Tensor)):
+            from ..ops.lm import sample_logits
+            # per-row settings reach their device and dtype once, here; scalars stay scalars
+            if isinstance(temperature, torch.Tensor):
+                temperature = temperature.to(device=dev, dtype=torch.float32).contiguous()
+            if isinstance(top_k, torch.Tensor):
+                top_k = top_k.to(device=dev, dtype=torch.int32).contiguous()
+            if isinstance(top_p, torch.Tensor):
+                top_p = top_p.to(device=dev, dtype=torch.float32).contiguous()
+            if isinstance(min_p, torch.Tensor):
+                min_p = min_p.to(device=dev, dtype=torch.float32).contiguous()
+            done = None if eos_id is None else torch.zeros(B, dtype=torch.uint8, device=dev)
+            for i in range(max_new_tokens):
+                u = torch.rand(B, generator=generator, device=dev)
+                tok = sample_logits(logits, u, temperature, top_k, top_p, min_p, eos_id, done)
+                out[:, i] = tok
+                if i + 1 < max_new_tokens:
+                    logits = self.decode_step(tok, cache)
+            return out
         finished = torch.zeros(B, dtype=torch.bool, device=dev)
         eos = None if eos_id is None else torch.full((), eos_id, dtype=torch.int64, device=dev)
         for i in range(max_new_tokens):

@@ -668,3 +668,136 @@ def mask_boundary_targets(inputs: torch.Tensor, targets: torch.Tensor, eos_id: i
     an EOS closes its own document, so the target at an EOS input is the first token of the next
     document, which document-masked attention has made unpredictable."""
     return targets.masked_fill(inputs == eos_id, ignore_index)
+
+
+# ------------------------------------------------------------------ sampling
+def _sample_scalars(temperature, top_k, top_p, min_p):
+    """Range checks of the scalar settings (tensors are clamped where they are used, never read back)."""
+    if not isinstance(temperature, torch.Tensor) and not (0.0 <= float(temperature) < float("inf")):
+        raise ValueError(f"sample_logits: temperature must be finite and >= 0, got {temperature}")
+    if top_k is not None and not isinstance(top_k, torch.Tensor) and int(top_k) < 1:
+        raise ValueError(f"sample_logits: top_k must be >= 1 or None, got {top_k}")
+    if top_p is not None and not isinstance(top_p, torch.Tensor) and not (0.0 < float(top_p) <= 1.0):
+        raise ValueError(f"sample_logits: top_p must lie in (0, 1], got {top_p}")
+    if min_p is not None and not isinstance(min_p, torch.Tensor) and not (0.0 <= float(min_p) <= 1.0):
+        raise ValueError(f"sample_logits: min_p must lie in [0, 1], got {min_p}")
+
+
+def _sample_rows(x, B, dev, dtype, default):
+    """A setting as a tensor [B]: a scalar (None: ``default``) repeated, or the caller's tensor converted."""
+    if isinstance(x, torch.Tensor):
+        if x.shape != (B,):
+            raise ValueError(f"sample_logits: a per-row setting must have shape [{B}], got {tuple(x.shape)}")
+        return x.to(device=dev, dtype=dtype)
+    return torch.full((B,), default if x is None else x, dtype=dtype, device=dev)
+
+
+def sample_logits_ref(logits: torch.Tensor, u: torch.Tensor, temperature=1.0, top_k=None, top_p=None, min_p=None,
+                      eos_id=None, finished=None, return_kept: bool = False):
+    """The contract of ``sample_logits`` in plain torch (the division by the temperature in fp32, weights and
+    sums in float64, a sort where the kernel descends by radix). Runs on any device."""
+    _sample_scalars(temperature, top_k, top_p, min_p)
+    if logits.dim() != 2 or logits.shape[1] < 1:
+        raise ValueError("sample_logits: logits must be [B, V] with V >= 1")
+    B, V = logits.shape
+    dev = logits.device
+    if u.shape != (B,):
+        raise ValueError(f"sample_logits: u must have shape [{B}]")
+    if (eos_id is None) != (finished is None):
+        raise ValueError("sample_logits: eos_id and finished come together")
+    tokens = torch.empty(B, dtype=torch.int64, device=dev)
+    kept = torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0:
+        return (tokens, kept) if return_kept else tokens
+    T = torch.nan_to_num(_sample_rows(temperature, B, dev, torch.float32, 1.0), nan=0.0).clamp(min=0)
+    k = _sample_rows(top_k, B, dev, torch.int64, V).clamp(min=1)
+    p = torch.nan_to_num(_sample_rows(top_p, B, dev, torch.float32, 1.0), nan=0.0).clamp(0, 1)
+    mp = torch.nan_to_num(_sample_rows(min_p, B, dev, torch.float32, 0.0), nan=0.0).clamp(0, 1)
+    ninf = torch.full((), float("-inf"), dtype=torch.float32, device=dev)
+    z = logits.float()
+    has_nan = torch.isnan(z).any(-1)
+    greedy = T == 0
+    s = torch.where(torch.isnan(z), ninf, z) / torch.where(greedy, torch.ones_like(T), T)[:, None]  # fp32
+    s = torch.where(torch.isnan(s), ninf, s) + 0.0
+    smax = s.max(-1).values
+    first_max = (s == smax[:, None]).int().argmax(-1)  # the lowest index of the maximum
+    plain = greedy | has_nan | ~torch.isfinite(smax)  # rows that get the arg max
+    w = torch.exp(s.double() - torch.where(plain, torch.zeros_like(smax), smax).double()[:, None])
+    keep = s > ninf
+    # top-k: everything >= the k-th largest value
+    sorted_s, order = s.sort(dim=-1, descending=True, stable=True)
+    kth = sorted_s.gather(1, (k.clamp(max=V) - 1)[:, None])
+    keep = keep & ((k >= V)[:, None] | (s >= kth))
+    # min-p
+    keep = keep & (w >= mp.double()[:, None])
+    # top-p: the largest kept value whose upper set holds top_p of the kept mass, ties kept
+    wk = torch.where(keep, w, torch.zeros_like(w))
+    cum = wk.gather(1, order).cumsum(-1)
+    reach = cum >= (p.double() * wk.sum(-1))[:, None]
+    cut = sorted_s.gather(1, reach.int().argmax(-1)[:, None])
+    keep = keep & (~(reach.any(-1) & (p < 1))[:, None] | (s >= cut))
+    # the draw, in vocabulary order
+    wk = torch.where(keep, w, torch.zeros_like(w))
+    cdf = wk.cumsum(-1)
+    hit = keep & (cdf >= (u.to(dev).double() * cdf[:, -1])[:, None])
+    last = V - 1 - keep.flip(-1).int().argmax(-1)
+    tok = torch.where(hit.any(-1), hit.int().argmax(-1), last)
+    tokens = torch.where(plain, first_max, tok)
+    kept = torch.where(plain, torch.ones_like(tok), keep.sum(-1)).int()
+    if finished is not None:
+        done = finished != 0
+        tokens = torch.where(done, torch.full_like(tokens, eos_id), tokens)
+        kept = torch.where(done, torch.zeros_like(kept), kept)
+        finished.copy_((done | (tokens == eos_id)).to(finished.dtype))
+    return (tokens, kept) if return_kept else tokens
+
+
+def sample_logits(logits: torch.Tensor, u: torch.Tensor, temperature=1.0, top_k=None, top_p=None, min_p=None,
+                  eos_id=None, finished=None, return_kept: bool = False):
+    """One token per row of ``logits`` [B, V]: temperature, top-k, min-p, top-p and the draw, on the GPU in one
+    launch (``csrc/kernels/sample.hip``) that holds no random state: ``u`` [B], fp32 in [0, 1), is the caller's.
+    Returns ``tokens`` int64 [B], with ``return_kept`` also ``kept`` int32 [B], the size of the set a row drew from.
+
+    With ``s = float(logits) / temperature`` in fp32 and ``smax`` a row's maximum (a ``-inf`` logit is never kept):
+    ``top_k`` (1 <= k < V) keeps every ``s >=`` the k-th largest value, ties at that value included; ``min_p``
+    (> 0) then keeps ``exp(s - smax) >= min_p``; ``top_p`` (< 1) then keeps ``s >= t*``, the largest kept value
+    whose upper set ``{s >= t*}`` holds at least ``top_p`` of the kept mass: the usual nucleus, except that tokens
+    tied at the cut are all kept. The token is the smallest kept index whose running mass, in vocabulary order,
+    reaches ``u`` times the kept mass; never an index outside the kept set. ``temperature == 0`` is greedy: the
+    lowest index of the maximum, ``kept = 1``, the filters ignored. A row with a NaN or without a finite ``s`` gets
+    some token in [0, V).
+
+    Each setting is a scalar for all rows or a tensor [B] (``top_k`` integer, ``k >= V`` for none), so one call
+    can mix a greedy row with sampled ones. Scalars are range-checked; tensors are clamped to the same ranges
+    where they are used, never read back. ``finished`` (uint8 or bool [B], with ``eos_id``) is updated in place:
+    a finished row gets ``eos_id`` (and ``kept = 0``), another row that draws ``eos_id`` becomes finished.
+
+    GPU logits in fp32, bf16 or fp16 with unit inner stride run the kernel (the same bits of ``tokens`` and
+    ``kept`` every run: integer sums only, no floating-point atomics); anything else ``sample_logits_ref``."""
+    if (logits.is_cuda and logits.dim() == 2 and logits.shape[1] >= 1 and logits.stride(1) == 1
+            and (logits.shape[0] <= 1 or logits.stride(0) >= logits.shape[1])
+            and logits.dtype in (torch.float32, torch.bfloat16, torch.float16) and u.is_cuda
+            and u.device == logits.device
+            and (finished is None or (finished.is_cuda and finished.dtype in (torch.uint8, torch.bool)
+                                      and finished.is_contiguous()))):
+        _sample_scalars(temperature, top_k, top_p, min_p)
+        B, dev = logits.shape[0], logits.device
+
+        def split(x, dtype, default):
+            if isinstance(x, torch.Tensor):
+                if x.shape != (B,):
+                    raise ValueError(f"sample_logits: a per-row setting must have shape [{B}], got {tuple(x.shape)}")
+                return default, x.to(device=dev, dtype=dtype).contiguous()
+            return (default if x is None else x), None
+
+        t_s, t_r = split(temperature, torch.float32, 1.0)
+        k_s, k_r = split(top_k, torch.int32, 0)
+        p_s, p_r = split(top_p, torch.float32, 1.0)
+        m_s, m_r = split(min_p, torch.float32, 0.0)
+        if (eos_id is None) != (finished is None):
+            raise ValueError("sample_logits: eos_id and finished come together")
+        fin = finished.view(torch.uint8) if finished is not None and finished.dtype == torch.bool else finished
+        tokens, kept = native.C().sample_logits(logits, u.float().contiguous(), float(t_s), min(int(k_s), 2**31 - 1),
+                                                float(p_s), float(m_s), t_r, k_r, p_r, m_r, eos_id, fin)
+        return (tokens, kept) if return_kept else tokens
+    return sample_logits_ref(logits, u, temperature, top_k, top_p, min_p, eos_id, finished, return_kept)

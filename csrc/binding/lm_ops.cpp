@@ -848,6 +848,58 @@ torch::Tensor attn_extend_paged(torch::Tensor q, torch::Tensor kp, torch::Tensor
   return o;
 }
 
+// fused sampler (sample.hip): logits [B, V] fp32 / bf16 / fp16 with unit inner stride, u fp32 [B] -> {tokens int64
+// [B], kept int32 [B]}. Each setting is a scalar, or a tensor [B] (fp32; top_k int32) that overrides it and is
+// clamped on the device, never read back; top_k 0: none. finished: uint8 [B], updated in place, with eos_id.
+std::vector<torch::Tensor> sample_logits(torch::Tensor logits, torch::Tensor u, double temperature, int64_t top_k,
+                                         double top_p, double min_p, c10::optional<torch::Tensor> temperature_t,
+                                         c10::optional<torch::Tensor> top_k_t, c10::optional<torch::Tensor> top_p_t,
+                                         c10::optional<torch::Tensor> min_p_t, c10::optional<int64_t> eos_id,
+                                         c10::optional<torch::Tensor> finished) {
+  const char* name = "sample_logits";
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2, name, ": logits must be a 2-D GPU tensor");
+  int dt;
+  if (logits.scalar_type() == at::kFloat) dt = CS_F32;
+  else if (logits.scalar_type() == at::kBFloat16) dt = CS_BF16;
+  else if (logits.scalar_type() == at::kHalf) dt = CS_F16;
+  else TORCH_CHECK(false, name, ": logits must be float32, bfloat16 or float16, got ", logits.scalar_type());
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V >= 1 && V < (1LL << 31) && B < (1LL << 31), name, ": need 1 <= V < 2^31 and B < 2^31");
+  TORCH_CHECK(logits.stride(1) == 1 && (B <= 1 || logits.stride(0) >= V), name,
+              ": logits rows must be contiguous (unit inner stride, row stride >= V)");
+  auto per_row = [&](const torch::Tensor& t, at::ScalarType st, const char* what) {
+    TORCH_CHECK(t.is_cuda() && t.device() == logits.device() && t.scalar_type() == st && t.dim() == 1 &&
+                    t.size(0) == B && t.is_contiguous(),
+                name, ": ", what, " must be a contiguous ", st, " [B] on the logits' device");
+  };
+  per_row(u, at::kFloat, "u");
+  if (temperature_t) per_row(*temperature_t, at::kFloat, "a per-row temperature");
+  if (top_k_t) per_row(*top_k_t, at::kInt, "a per-row top_k");
+  if (top_p_t) per_row(*top_p_t, at::kFloat, "a per-row top_p");
+  if (min_p_t) per_row(*min_p_t, at::kFloat, "a per-row min_p");
+  TORCH_CHECK(finished.has_value() == eos_id.has_value(), name, ": eos_id and finished come together");
+  if (finished) per_row(*finished, at::kByte, "finished");
+  TORCH_CHECK(temperature >= 0.0 && std::isfinite(temperature), name, ": temperature must be finite and >= 0");
+  TORCH_CHECK(top_k >= 0 && top_k <= INT_MAX, name, ": top_k must be >= 1 (0: none)");
+  TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, name, ": top_p must lie in (0, 1]");
+  TORCH_CHECK(min_p >= 0.0 && min_p <= 1.0, name, ": min_p must lie in [0, 1]");
+  // a positive double below the smallest float would round to 0, which means something else
+  const float tf = temperature > 0.0 ? std::max((float)temperature, FLT_MIN) : 0.f;
+  const float pf = std::max((float)top_p, FLT_MIN);
+  DevGuard g(logits.device());
+  auto tokens = torch::empty({B}, logits.options().dtype(at::kLong));
+  auto kept = torch::empty({B}, logits.options().dtype(at::kInt));
+  if (B == 0) return {tokens, kept};
+  CS_LAUNCH(cs_sample_logits(dt, logits.data_ptr(), B > 1 ? logits.stride(0) : V, (int)B, (int)V, u.data_ptr<float>(),
+                             temperature_t ? temperature_t->data_ptr<float>() : nullptr, tf,
+                             top_k_t ? top_k_t->data_ptr<int>() : nullptr, (int)top_k,
+                             top_p_t ? top_p_t->data_ptr<float>() : nullptr, pf,
+                             min_p_t ? min_p_t->data_ptr<float>() : nullptr, (float)min_p,
+                             finished ? finished->data_ptr<uint8_t>() : nullptr, eos_id ? *eos_id : -1,
+                             tokens.data_ptr<int64_t>(), kept.data_ptr<int>(), cur_stream()));
+  return {tokens, kept};
+}
+
 // C = a @ b on the bf16 matrix cores (gemm_bf16.hip). a: [M, K], b: [K, N], bf16, each with unit
 // stride along one of its two dimensions (so x @ w.t(), dy @ w and dy.t() @ x all run without a
 // copy); out: a new bf16 (out_f32 false) or fp32 [M, N] tensor, or `acc` [M, N] += a @ b (fp32, or
@@ -1009,6 +1061,13 @@ void register_lm_ops(pybind11::module& m) {
         "attn_extend against bf16 pools [P,page,Hkv,D] through block_table int32 [B,C]; an entry outside [0,P) masks "
         "its keys", py::arg("q"), py::arg("k_pages"), py::arg("v_pages"), py::arg("block_table"), py::arg("start"),
         py::arg("scale"), py::arg("counts") = c10::nullopt);
+  m.def("sample_logits", &sample_logits,
+        "fused sampler: one token per row of logits [B,V] by temperature, top-k, min-p, top-p and an inverse-CDF draw at "
+        "u fp32 [B] -> (tokens int64 [B], kept int32 [B]); a *_rows tensor [B] overrides its scalar; top_k 0: none",
+        py::arg("logits"), py::arg("u"), py::arg("temperature") = 1.0, py::arg("top_k") = 0, py::arg("top_p") = 1.0,
+        py::arg("min_p") = 0.0, py::arg("temperature_rows") = c10::nullopt, py::arg("top_k_rows") = c10::nullopt,
+        py::arg("top_p_rows") = c10::nullopt, py::arg("min_p_rows") = c10::nullopt, py::arg("eos_id") = c10::nullopt,
+        py::arg("finished") = c10::nullopt);
   m.def("decode_key_tile", &cs_attn_decode_key_tile, "keys a workgroup of the decode kernel reads per trip");
   m.def("decode_splits", [](int64_t B, int64_t Hkv, int64_t Smax) {
           TORCH_CHECK(B >= 0 && Hkv >= 0 && Smax >= 0 && B <= INT_MAX && Hkv <= INT_MAX && Smax <= INT_MAX,

@@ -350,7 +350,7 @@ hipError_t cs_clock_stamp(unsigned long long* slots, int i, hipStream_t stream);
 hipError_t cs_clock_stop(int* stop, hipStream_t stream);
 
 // ---------------------------------------------------------------- decoder-LM elementwise ops (lm.hip)
-enum { CS_F32 = 0, CS_BF16 = 1 };
+enum { CS_F32 = 0, CS_BF16 = 1, CS_F16 = 2 };  // CS_F16: the sampler's logits only
 int cs_rmsnorm_bwd_partials(int rows, int D);
 // whether RMSNorm of width D runs the 4-wide kernels (D % 4 == 0 and D <= 8192): their 16-byte (fp32) /
 // 8-byte (bf16) accesses need x, w, y, g, dx and dw 16-byte aligned, and only they mix dtypes
@@ -520,6 +520,17 @@ hipError_t cs_gemm_bf16_bn_stats(const void* A, int64_t lda, const void* B, int6
 int cs_gemm_bf16_splits(int M, int N, int K);
 hipError_t cs_gemm_bf16(int a_kmajor, const void* A, int64_t lda, int b_kmajor, const void* B, int64_t ldb, void* C,
                         int64_t ldc, int M, int N, int K, int out_mode, int splits, int64_t slab, hipStream_t stream);
+// Fused sampler (sample.hip; contract in docs/sampling.md): one token per row of logits [B, V] (dt CS_F32, CS_BF16
+// or CS_F16, unit inner stride, row_stride >= V elements) by temperature, top-k, min-p, top-p and an inverse-CDF
+// draw at u [B] fp32 in [0, 1), one workgroup per row, no floating-point atomics. Each setting is a device array
+// [B] (fp32; top_k int32), clamped on the device, or null with the scalar that follows it: temperature_s >= 0
+// (0: argmax), top_k_s >= 1 or 0 for none, 0 < top_p_s <= 1, 0 <= min_p_s <= 1. finished: uint8 [B] or null; a
+// row with finished[b] != 0 gets eos_id, any other row that draws eos_id sets it. tokens int64 [B]; kept int32
+// [B]: the size of the set the token was drawn from. hipErrorInvalidValue on anything else.
+hipError_t cs_sample_logits(int dt, const void* logits, int64_t row_stride, int B, int V, const float* u,
+                            const float* temperature, float temperature_s, const int* top_k, int top_k_s,
+                            const float* top_p, float top_p_s, const float* min_p, float min_p_s,
+                            unsigned char* finished, int64_t eos_id, int64_t* tokens, int* kept, hipStream_t stream);
 hipError_t cs_rope(int dt, const void* x, const float* cosv, const float* sinv, void* out, int B, int S, int H, int hd,
                    int inverse, hipStream_t s);
 // QK-norm fused with RoPE: per head-row of q [B, S, Hq, hd] and k [B, S, Hkv, hd] (one dtype dt, hd 64 or

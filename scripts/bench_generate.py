@@ -6,6 +6,8 @@ without a cache, a loop that re-runs the full forward on the growing sequence.
   --arm naive     for every new token: model(tokens)[:, -1].argmax(-1), appended to tokens
   --kv fp8        (generate arm) an FP8 KV cache: model.generate(..., kv_dtype="fp8")
   --page-size N   (generate arm) a paged KV cache of N positions per page: model.generate(..., page_size=N)
+  --temperature T --top-k K --top-p P   (generate arm) sampled instead of greedy, a seeded device generator
+  --sampler fused (generate arm) the fused sampler (ops.lm.sample_logits) instead of the chain of torch ops
 
 llama3-1b, B 8, prompt 128, 128 new tokens by default; random weights (seeded) and a random prompt. One
 process per arm; after one untimed warm-up run, each timed run ends in a device synchronise and the median
@@ -33,9 +35,15 @@ def main() -> int:
     ap.add_argument("--prompt", type=int, default=128)
     ap.add_argument("--new", type=int, default=128)
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--temperature", type=float, default=0.0, help="0: greedy")
+    ap.add_argument("--top-k", type=int, default=0, help="0: none")
+    ap.add_argument("--top-p", type=float, default=0.0, help="0: none (given: the fused sampler runs)")
+    ap.add_argument("--sampler", choices=["fused"], default=None)
     a = ap.parse_args()
     if a.arm == "naive" and (a.kv != "bf16" or a.page_size):
         ap.error("--arm naive has no KV cache")
+    if a.arm == "naive" and (a.temperature or a.top_k or a.top_p or a.sampler):
+        ap.error("--arm naive is greedy")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_generate: needs a GPU")
@@ -50,7 +58,9 @@ def main() -> int:
     prompt = torch.randint(0, model.cfg.vocab_size, (a.batch, a.prompt), device=dev)
 
     def generate():
-        return model.generate(prompt, a.new, kv_dtype="fp8" if a.kv == "fp8" else None, page_size=a.page_size or None)
+        return model.generate(prompt, a.new, kv_dtype="fp8" if a.kv == "fp8" else None, page_size=a.page_size or None,
+                              temperature=a.temperature, top_k=a.top_k or None, top_p=a.top_p or None,
+                              sampler=a.sampler, generator=torch.Generator(device=dev).manual_seed(1))
 
     def naive():
         tokens = prompt
@@ -71,6 +81,7 @@ def main() -> int:
     assert out.shape == (a.batch, a.new)
     med = statistics.median(secs)
     print(json.dumps({"arm": a.arm, "kv": a.kv, "page_size": a.page_size, "model": a.model, "batch": a.batch, "prompt": a.prompt, "new": a.new,
+                      "temperature": a.temperature, "top_k": a.top_k, "top_p": a.top_p, "sampler": a.sampler,
                       "runs": a.runs, "s_median": round(med, 4), "s_min": round(min(secs), 4),
                       "s_max": round(max(secs), 4), "tokens_per_s": round(a.batch * a.new / med, 1),
                       "ms_per_token_step": round(med / a.new * 1e3, 3),
