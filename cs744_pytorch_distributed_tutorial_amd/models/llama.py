@@ -324,6 +324,27 @@ class Llama(nn.Module):
                 h = blk(h, cos, sin, doc)
         return self.norm(h)
 
+    # ------------------------------------------------------------------ FP8 weights for inference
+    def quantize_weights_(self, dtype: str = "fp8", head: bool = True) -> "Llama":
+        """Replace, in place, the seven projections of every block (and the vocabulary head when ``head``) with
+        ``ops.linear_fp8.Fp8Linear``: float8_e4m3fn codes and one power-of-two scale per output channel. The
+        fp32 master weights and their bf16 shadows are dropped; embeddings and norms are untouched. The model
+        is inference only afterwards: ``prefill``, ``extend``, ``decode_step`` and ``generate`` work as before,
+        with decode steps and short extends on the gfx950 FP8 linear kernel. Idempotent."""
+        if dtype != "fp8":
+            raise ValueError(f"quantize_weights_: only dtype 'fp8' is supported, got {dtype!r}")
+        from ..ops.linear_fp8 import Fp8Linear
+        owners = [(blk.attention, ("wq", "wk", "wv", "wo")) for blk in self.layers]
+        owners += [(blk.feed_forward, ("w1", "w3", "w2")) for blk in self.layers]
+        if head:
+            owners.append((self, ("output",)))
+        for mod, names in owners:
+            for name in names:
+                lin = getattr(mod, name)
+                if not isinstance(lin, Fp8Linear):
+                    setattr(mod, name, Fp8Linear.from_linear(lin))
+        return self
+
     # ------------------------------------------------------------------ inference with a KV cache
     def cache_dtype(self, device) -> torch.dtype:
         """The dtype the projections come out in on ``device``: the autocast dtype under GPU autocast,

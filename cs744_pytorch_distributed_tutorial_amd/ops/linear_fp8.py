@@ -1,0 +1,131 @@
+"""FP8 weight-only projections for decoding (W8A16): ``csrc/kernels/linear_fp8.hip``.
+
+A weight ``[N, K]`` is stored as float8_e4m3fn codes plus one power-of-two fp32 scale per output channel, the
+format ``ops.attention.kv_quantize_ref`` defines, applied to the rows of the weight. Every code is exactly a
+bf16 number and ``float(code) * scale`` is the weight, so the kernel's only roundings are its fp32 sums and
+the bf16 store. At decode batch sizes a projection is bound by its weight bytes, which this halves against
+the bf16 shadow. Inference only. ``docs/linear_fp8.md`` has the design and the measurements."""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+
+from . import native
+from .attention import FP8, _no_grad_inputs, kv_dequantize, kv_quantize_ref
+
+
+def quantize_weight_fp8(w: torch.Tensor) -> tuple:
+    """``w`` ``[N, K]`` (fp32, bf16 or fp64, any device) -> ``(codes float8_e4m3fn [N, K], scale fp32 [N])``:
+    ``kv_quantize_ref`` on the rows, one scale per output channel."""
+    if w.dim() != 2:
+        raise ValueError(f"quantize_weight_fp8: the weight must be [N, K], got {tuple(w.shape)}")
+    return kv_quantize_ref(w.detach())
+
+
+def linear_fp8_ref(x: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """``x @ (codes * scale[:, None])^T`` in plain torch: fp32 math (fp64 for an fp64 ``x``), the result in
+    ``x``'s dtype. ``x`` ``[..., K]``."""
+    ct = torch.float64 if x.dtype == torch.float64 else torch.float32
+    w = codes.to(ct) * scale.to(ct).unsqueeze(-1)
+    return (x.to(ct) @ w.t()).to(x.dtype)
+
+
+def linear_fp8_max_m() -> int:
+    """The most rows of ``x`` the kernel takes."""
+    return native.C().linear_fp8_max_m()
+
+
+def linear_fp8_splits(M: int, N: int, K: int) -> int:
+    """The K slabs the kernel splits K into, and sums in order, for these shapes: from M, N, K and the CU count
+    only, never from data. (``linear_fp8``'s ``splits`` argument does not change this count: see there.)"""
+    return native.C().linear_fp8_splits(M, N, K)
+
+
+def linear_fp8_native_ok(x2: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor) -> bool:
+    """Whether ``linear_fp8_kernel`` takes these operands: everything on one GPU, ``x2`` bf16 ``[M, K]`` with
+    unit inner stride and M at most ``linear_fp8_max_m()``, ``codes`` float8_e4m3fn ``[N, K]`` K-contiguous,
+    ``scale`` fp32 ``[N]`` contiguous, K a multiple of 64, N a multiple of 8, row strides that keep every row
+    16-byte aligned, and 16-byte aligned base pointers."""
+    if not (x2.is_cuda and codes.is_cuda and scale.is_cuda and codes.device == x2.device == scale.device):
+        return False
+    if x2.dtype != torch.bfloat16 or codes.dtype != FP8 or scale.dtype != torch.float32:
+        return False
+    if x2.dim() != 2 or codes.dim() != 2 or scale.dim() != 1:
+        return False
+    (M, K), N = x2.shape, codes.shape[0]
+    if codes.shape[1] != K or scale.shape[0] != N or M > linear_fp8_max_m():
+        return False
+    if M == 0 or N == 0:
+        return True  # an empty result, no launch
+    if K < 64 or K % 64 != 0 or N % 8 != 0:
+        return False
+    if x2.stride(1) != 1 or (M > 1 and (x2.stride(0) < K or x2.stride(0) % 8 != 0)):
+        return False
+    if codes.stride(1) != 1 or (N > 1 and (codes.stride(0) < K or codes.stride(0) % 16 != 0)):
+        return False
+    return scale.is_contiguous() and all(t.data_ptr() % 16 == 0 for t in (x2, codes, scale))
+
+
+def _dequant_mm(x2: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """The slow path on the GPU for bf16 ``x2``: the weight dequantised to bf16 (exact), then the bf16 GEMM"""
+    from .lm import _mm
+    with torch.autocast("cuda", enabled=False):
+        return _mm(x2, kv_dequantize(codes, scale, torch.bfloat16).t())
+
+
+def linear_fp8(x: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor, splits: Optional[int] = None,
+               slabs: Optional[int] = None) -> torch.Tensor:
+    """``y[..., N] = x[..., K] @ (codes[N, K] * scale[N, None])^T`` in ``x``'s dtype.
+
+    The gfx950 kernel runs when ``linear_fp8_native_ok`` holds for ``x`` flattened to ``[M, K]``: decode steps
+    and short extends (M up to ``linear_fp8_max_m()``). Anything else takes the slow path: on the GPU with a
+    bf16 ``x`` the weight is dequantised to bf16 and multiplied by the bf16 GEMM of ``ops.lm`` (a prefill reads
+    and writes the whole weight once more per call; a kernel for large M is future work), and everywhere else
+    ``linear_fp8_ref`` runs.
+
+    The kernel cuts K into slabs and sums them in a fixed order. ``slabs`` is their number: ``None`` is
+    ``linear_fp8_splits(M, N, K)``, anything else is clamped into [1, K / 128]; it fixes the summation order and
+    so the last bits of the result. ``splits`` is a workgroup count, not a slab count: how many workgroups share
+    the slabs of a channel tile (``None``: one per slab; otherwise clamped into [1, slabs]). It moves work and
+    changes no bit of the result. Both are ignored off the kernel. Inference only."""
+    _no_grad_inputs("linear_fp8", x, scale)
+    K = x.shape[-1]
+    x2 = x.reshape(-1, K)
+    if linear_fp8_native_ok(x2, codes, scale):
+        with torch.no_grad():
+            y = native.C().linear_fp8(x2, codes, scale, 0 if splits is None else max(int(splits), 1),
+                                      0 if slabs is None else max(int(slabs), 1))
+    elif x2.is_cuda and x2.dtype == torch.bfloat16 and codes.is_cuda:
+        y = _dequant_mm(x2, codes, scale)
+    else:
+        y = linear_fp8_ref(x2, codes, scale)
+    return y.view(*x.shape[:-1], codes.shape[0])
+
+
+class Fp8Linear(torch.nn.Module):
+    """A bias-free projection whose weight is FP8 codes (buffer ``weight`` ``[out, in]``) and per-channel scales
+    (buffer ``weight_scale`` ``[out]``). Inference only: an input that requires grad raises. Under bf16 GPU
+    autocast the input is cast to bf16, as ``ShadowLinear`` does, and the result is bf16."""
+
+    def __init__(self, in_features: int, out_features: int, device=None):
+        super().__init__()
+        self.in_features, self.out_features = in_features, out_features
+        self.register_buffer("weight", torch.zeros(out_features, in_features, dtype=torch.uint8, device=device).view(FP8))
+        self.register_buffer("weight_scale", torch.ones(out_features, device=device))
+
+    @classmethod
+    def from_linear(cls, lin: torch.nn.Linear) -> "Fp8Linear":
+        if lin.bias is not None:
+            raise ValueError("Fp8Linear.from_linear: the projection must be bias-free")
+        m = cls(lin.in_features, lin.out_features, device=lin.weight.device)
+        m.weight, m.weight_scale = quantize_weight_fp8(lin.weight)
+        return m
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.is_cuda and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16:
+            x = x.to(torch.bfloat16)
+        return linear_fp8(x, self.weight, self.weight_scale)
+
+    def extra_repr(self) -> str:
+        return f"in_features={self.in_features}, out_features={self.out_features}, weight=float8_e4m3fn"

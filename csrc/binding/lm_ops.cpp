@@ -966,6 +966,48 @@ torch::Tensor mm_bf16(torch::Tensor a, torch::Tensor b, bool out_f32, c10::optio
   return c;
 }
 
+// FP8 weight-only linear (linear_fp8.hip): x bf16 [M, K] with unit inner stride, codes float8_e4m3fn [N, K] with
+// unit inner stride, scale fp32 [N] contiguous -> y bf16 [M, N] = (x . codes^T) * scale. M <= linear_fp8_max_m(),
+// K % 64 == 0, N % 8 == 0. K is summed in `slabs` slabs (0 = cs_linear_fp8_splits(M, N, K), otherwise clamped into
+// [1, cs_linear_fp8_max_splits(K)]): the slab count fixes the summation order and so the bits. splits (0 = one
+// workgroup per slab, otherwise clamped into [1, slabs]) is the number of workgroups that share the slabs of a
+// channel tile and changes no bit. An empty x or weight gives an empty y whatever K and N are.
+torch::Tensor linear_fp8(torch::Tensor x, torch::Tensor codes, torch::Tensor scale, int64_t splits, int64_t slabs_arg) {
+  for (auto* t : {&x, &codes, &scale}) TORCH_CHECK(t->is_cuda(), "linear_fp8: all tensors must be GPU tensors");
+  TORCH_CHECK(codes.device() == x.device() && scale.device() == x.device(), "linear_fp8: all tensors must be on one device");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "linear_fp8: x must be bfloat16");
+  TORCH_CHECK(codes.scalar_type() == at::kFloat8_e4m3fn, "linear_fp8: codes must be float8_e4m3fn");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat, "linear_fp8: scale must be float32");
+  TORCH_CHECK(x.dim() == 2 && codes.dim() == 2 && scale.dim() == 1, "linear_fp8: x [M, K], codes [N, K], scale [N]");
+  const int64_t M = x.size(0), K = x.size(1), N = codes.size(0);
+  TORCH_CHECK(codes.size(1) == K && scale.size(0) == N, "linear_fp8: x [M, K], codes [N, K] and scale [N] must agree");
+  DevGuard g(x.device());
+  auto y = torch::empty({M, N}, x.options());
+  if (M == 0 || N == 0) return y;
+  TORCH_CHECK(M <= cs_linear_fp8_max_m(), "linear_fp8: M must be at most ", cs_linear_fp8_max_m(), ", got ", M);
+  TORCH_CHECK(K >= 64 && K % 64 == 0 && K <= INT_MAX, "linear_fp8: K must be a positive multiple of 64, got ", K);
+  TORCH_CHECK(N % 8 == 0 && N <= INT_MAX, "linear_fp8: N must be a multiple of 8, got ", N);
+  TORCH_CHECK(x.stride(1) == 1 && (M == 1 || (x.stride(0) >= K && x.stride(0) % 8 == 0)),
+              "linear_fp8: x needs unit inner stride and a row stride >= K that is a multiple of 8");
+  TORCH_CHECK(codes.stride(1) == 1 && (N == 1 || (codes.stride(0) >= K && codes.stride(0) % 16 == 0)),
+              "linear_fp8: codes need unit inner stride and a row stride >= K that is a multiple of 16");
+  TORCH_CHECK(scale.is_contiguous(), "linear_fp8: scale must be contiguous");
+  check_aligned(x, "x"); check_aligned(codes, "codes"); check_aligned(scale, "scale"); check_aligned(y, "y");
+  const int slabs = slabs_arg == 0 ? cs_linear_fp8_splits((int)M, (int)N, (int)K)
+                                  : (int)std::min<int64_t>(std::max<int64_t>(slabs_arg, 1), cs_linear_fp8_max_splits((int)K));
+  const int wgs = splits == 0 ? slabs : (int)std::min<int64_t>(std::max<int64_t>(splits, 1), slabs);
+  torch::Tensor ws;
+  float* wsp = nullptr;
+  if (slabs > 1) {
+    ws = torch::empty({(int64_t)cs_linear_fp8_ws_floats((int)M, (int)N, slabs)}, x.options().dtype(at::kFloat));
+    wsp = ws.data_ptr<float>();
+  }
+  CS_LAUNCH(cs_linear_fp8(x.data_ptr(), codes.data_ptr(), scale.data_ptr<float>(), y.data_ptr(), wsp, (int)M, (int)N,
+                          (int)K, (size_t)(M == 1 ? K : x.stride(0)), (size_t)(N == 1 ? K : codes.stride(0)), slabs, wgs,
+                          cur_stream()));
+  return y;
+}
+
 // y = a @ b (bf16, a [M, K] K-major, b [K, N] with unit stride along K) plus the BatchNorm
 // statistics of y per 256-row tile: {y, tiles [ceil(M / 256), N, 2] = (mean, M2)}
 std::vector<torch::Tensor> mm_bf16_bn_stats(torch::Tensor a, torch::Tensor b) {
@@ -1075,6 +1117,18 @@ void register_lm_ops(pybind11::module& m) {
           return cs_attn_decode_splits((int)B, (int)Hkv, (int)Smax);
         }, "the key splits attn_decode picks for these shapes (never from lens)", py::arg("B"), py::arg("Hkv"),
         py::arg("Smax"));
+  m.def("linear_fp8", &linear_fp8,
+        "FP8 weight-only linear: x bf16 [M,K], codes float8_e4m3fn [N,K], scale fp32 [N] -> bf16 [M,N]; M <= "
+        "linear_fp8_max_m(), K % 64 == 0, N % 8 == 0; splits: workgroups sharing the K slabs of a channel tile (0: one "
+        "per slab; no effect on the bits); slabs: the K slabs summed in order (0: linear_fp8_splits(M, N, K))",
+        py::arg("x"), py::arg("codes"), py::arg("scale"), py::arg("splits") = 0, py::arg("slabs") = 0);
+  m.def("linear_fp8_splits", [](int64_t M, int64_t N, int64_t K) {
+          TORCH_CHECK(M >= 0 && N >= 0 && K >= 0 && M <= INT_MAX && N <= INT_MAX && K <= INT_MAX,
+                      "linear_fp8_splits: sizes out of range");
+          return cs_linear_fp8_splits((int)M, (int)N, (int)K);
+        }, "the K slabs linear_fp8 sums for these shapes (from M, N, K and the CU count, never from data)", py::arg("M"),
+        py::arg("N"), py::arg("K"));
+  m.def("linear_fp8_max_m", &cs_linear_fp8_max_m, "the most rows of x the FP8 linear kernel takes");
   m.def("mm_bf16", &mm_bf16, "C = a @ b on the bf16 matrix cores", pybind11::arg("a"), pybind11::arg("b"),
         pybind11::arg("out_f32") = false, pybind11::arg("acc") = c10::nullopt, pybind11::arg("splits") = -1);
   m.def("mm_bf16_bn_stats", &mm_bf16_bn_stats, "a @ b (bf16) plus per-256-row-tile BatchNorm (mean, M2) of the result");

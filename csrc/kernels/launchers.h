@@ -418,6 +418,21 @@ hipError_t cs_attn_fwd_doc(const void* q, const void* k, const void* v, void* o,
 hipError_t cs_attn_bwd_doc(const void* q, const void* k, const void* v, const void* o, const void* dout,
                            const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int S, int Hq, int Hkv,
                            int D, float scale, const int* kstart, const int* qend, hipStream_t stream);
+// FP8 weight-only linear for decoding (linear_fp8.hip): y[M, N] = (x[M, K] . codes[N, K]^T) * scale[N]. x bf16 with
+// rows ldx elements apart (% 8 == 0, >= K), codes e4m3fn bytes with rows ldw bytes apart (% 16 == 0, >= K), scale
+// fp32 [N] (powers of two, one per output channel: the format of kv_quant_device.h on the rows of the weight), y
+// bf16 [M, N] contiguous; 0 <= M <= cs_linear_fp8_max_m(), K % 64 == 0, N % 8 == 0, x / codes / scale / y 16-byte
+// aligned. K is summed in `slabs` contiguous slabs, 1 <= slabs <= cs_linear_fp8_max_splits(K), combined in slab
+// order (no atomics); ws: cs_linear_fp8_ws_floats floats, 16-byte aligned (may be null when slabs == 1). The slab
+// count alone fixes the summation order; wgs in [1, slabs] is how many workgroups share the slabs of a channel
+// tile and changes no bit of y. M == 0 or N == 0 launches nothing. hipErrorInvalidValue on anything else.
+int cs_linear_fp8_max_m();
+int cs_linear_fp8_max_splits(int K);
+int cs_linear_fp8_splits(int M, int N, int K);  // the default slab count: from M, N, K and the CU count only
+size_t cs_linear_fp8_ws_floats(int M, int N, int slabs);
+hipError_t cs_linear_fp8(const void* x, const void* codes, const float* scale, void* y, float* ws, int M, int N, int K,
+                         size_t ldx, size_t ldw, int slabs, int wgs, hipStream_t stream);
+
 // decode attention against a KV cache, split over the keys (attn_decode.hip). q / o: bf16 [B, Hq, D]; kc / vc:
 // bf16 [B, Smax, Hkv, D] with row stride Hkv * D and batch stride `batch_stride` elements (% 8 == 0, so a
 // [:, :n] slice of a longer cache is an operand); lens: int32 [B] on the device, clamped into [0, Smax] in
