@@ -102,6 +102,7 @@ class Attention(nn.Module):
         self.wk = _Linear(cfg.dim, self.nkv * self.hd, bias=False)
         self.wv = _Linear(cfg.dim, self.nkv * self.hd, bias=False)
         self.wo = _Linear(self.nh * self.hd, cfg.dim, bias=False)
+        self.fused_fp8 = False  # set by Llama.quantize_weights_(fused=True)
         self.qk_norm = cfg.qk_norm
         if self.qk_norm:
             self.q_norm = RMSNorm(self.hd, cfg.norm_eps)
@@ -111,9 +112,12 @@ class Attention(nn.Module):
         """The projections of ``x`` [B, S, dim] as [B, S, H, hd], q and k after (QK-norm and) RoPE with the
         table rows ``cos`` / ``sin`` [S, hd/2]: row s of the tables belongs to position s of the S axis."""
         B, S, _ = x.shape
-        q = self.wq(x).view(B, S, self.nh, self.hd)
-        k = self.wk(x).view(B, S, self.nkv, self.hd)
-        v = self.wv(x).view(B, S, self.nkv, self.hd)
+        if self.fused_fp8:  # one grouped launch for the three FP8 projections (ops.linear_fp8.linear_fp8_grouped)
+            from ..ops.linear_fp8 import autocast_input, linear_fp8_grouped
+            q, k, v = linear_fp8_grouped(autocast_input(x), [(w.weight, w.weight_scale) for w in (self.wq, self.wk, self.wv)])
+        else:
+            q, k, v = self.wq(x), self.wk(x), self.wv(x)
+        q, k, v = q.view(B, S, self.nh, self.hd), k.view(B, S, self.nkv, self.hd), v.view(B, S, self.nkv, self.hd)
         if self.qk_norm:
             q, k = _ops().qk_norm_rope(q, k, self.q_norm.weight, self.k_norm.weight, cos, sin, self.q_norm.eps)
         else:
@@ -227,8 +231,13 @@ class FeedForward(nn.Module):
         self.w1 = _Linear(cfg.dim, cfg.ffn_dim, bias=False)  # gate
         self.w3 = _Linear(cfg.dim, cfg.ffn_dim, bias=False)  # up
         self.w2 = _Linear(cfg.ffn_dim, cfg.dim, bias=False)  # down
+        self.fused_fp8 = False  # set by Llama.quantize_weights_(fused=True)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.fused_fp8:  # gate, up and SwiGLU in one launch (ops.linear_fp8.swiglu_linear_fp8)
+            from ..ops.linear_fp8 import autocast_input, swiglu_linear_fp8
+            return self.w2(swiglu_linear_fp8(autocast_input(x), self.w1.weight, self.w1.weight_scale, self.w3.weight,
+                                             self.w3.weight_scale))
         return self.w2(_ops().swiglu(self.w1(x), self.w3(x)))
 
 
@@ -325,12 +334,17 @@ class Llama(nn.Module):
         return self.norm(h)
 
     # ------------------------------------------------------------------ FP8 weights for inference
-    def quantize_weights_(self, dtype: str = "fp8", head: bool = True) -> "Llama":
+    def quantize_weights_(self, dtype: str = "fp8", head: bool = True, fused: bool = False) -> "Llama":
         """Replace, in place, the seven projections of every block (and the vocabulary head when ``head``) with
         ``ops.linear_fp8.Fp8Linear``: float8_e4m3fn codes and one power-of-two scale per output channel. The
         fp32 master weights and their bf16 shadows are dropped; embeddings and norms are untouched. The model
         is inference only afterwards: ``prefill``, ``extend``, ``decode_step`` and ``generate`` work as before,
-        with decode steps and short extends on the gfx950 FP8 linear kernel. Idempotent."""
+        with decode steps and short extends on the gfx950 FP8 linear kernel. Idempotent.
+
+        ``fused=True`` (opt-in) also makes every block project q, k and v in one grouped launch
+        (``ops.linear_fp8.linear_fp8_grouped``) and run gate, up and SwiGLU in one (``swiglu_linear_fp8``): the same
+        buffers and ``state_dict``, 4 launches where a decode step made 11, and logits that differ from the
+        separate calls' only as a different K-slab count makes them differ (docs/linear_fp8.md)."""
         if dtype != "fp8":
             raise ValueError(f"quantize_weights_: only dtype 'fp8' is supported, got {dtype!r}")
         from ..ops.linear_fp8 import Fp8Linear
@@ -343,6 +357,8 @@ class Llama(nn.Module):
                 lin = getattr(mod, name)
                 if not isinstance(lin, Fp8Linear):
                     setattr(mod, name, Fp8Linear.from_linear(lin))
+        for blk in self.layers:
+            blk.attention.fused_fp8 = blk.feed_forward.fused_fp8 = bool(fused)
         return self
 
     # ------------------------------------------------------------------ inference with a KV cache

@@ -103,6 +103,89 @@ def linear_fp8(x: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor, splits
     return y.view(*x.shape[:-1], codes.shape[0])
 
 
+def linear_fp8_grouped_splits(M: int, Ns, K: int) -> int:
+    """The K slabs ``linear_fp8_grouped`` sums for weights of ``Ns`` output channels: ``linear_fp8_splits``'s rule on
+    the summed 32-channel tiles of all weights, from the shapes and the CU count only."""
+    return native.C().linear_fp8_grouped_splits(M, [int(n) for n in Ns], K)
+
+
+def swiglu_linear_fp8_splits(M: int, N: int, K: int) -> int:
+    """The K slabs ``swiglu_linear_fp8`` sums: the same rule on its ``ceil(N / 16)`` workgroups per slab."""
+    return native.C().swiglu_linear_fp8_splits(M, N, K)
+
+
+def _fused_ok(x2: torch.Tensor, weights) -> bool:
+    """every operand passes ``linear_fp8_native_ok`` and nothing is empty (an empty result needs no kernel)"""
+    return x2.shape[0] > 0 and all(c.dim() == 2 and c.shape[0] > 0 and linear_fp8_native_ok(x2, c, s)
+                                   for c, s in weights)
+
+
+def _grouped_composition(x, weights, splits, slabs) -> tuple:
+    return tuple(linear_fp8(x, c, s, splits, slabs) for c, s in weights)
+
+
+def _swiglu_composition(x, gate_codes, gate_scale, up_codes, up_scale, splits, slabs) -> torch.Tensor:
+    from .lm import swiglu
+    return swiglu(linear_fp8(x, gate_codes, gate_scale, splits, slabs), linear_fp8(x, up_codes, up_scale, splits, slabs))
+
+
+def linear_fp8_grouped(x: torch.Tensor, weights, splits: Optional[int] = None, slabs: Optional[int] = None) -> tuple:
+    """``linear_fp8(x, codes_i, scale_i)`` for 1 to 3 ``(codes, scale)`` pairs that share ``x`` (q, k and v), as a
+    tuple. When every pair passes ``linear_fp8_native_ok`` one grouped launch of the gfx950 kernel computes all of
+    them (and one combine, when K is split): every weight stays its own tensor, and the narrow ones ride in the grid
+    of the wide one. Each result has the bits ``linear_fp8`` gives at the same ``slabs``; ``None`` is
+    ``linear_fp8_grouped_splits``, picked from the summed tiles, so it can differ from what the separate calls
+    pick. ``splits`` as in ``linear_fp8``. Anything the kernel does not take is ``linear_fp8`` per weight."""
+    weights = [tuple(w) for w in weights]
+    if not 1 <= len(weights) <= 3 or any(len(w) != 2 for w in weights):
+        raise ValueError(f"linear_fp8_grouped: 1 to 3 (codes, scale) pairs, got {len(weights)}")
+    K = x.shape[-1]
+    for codes, scale in weights:
+        if codes.dim() != 2 or codes.shape[1] != K or scale.shape != codes.shape[:1]:
+            raise ValueError(f"linear_fp8_grouped: codes {tuple(codes.shape)} and scale {tuple(scale.shape)} do not "
+                             f"match x [..., {K}]")
+    _no_grad_inputs("linear_fp8_grouped", x, *(s for _, s in weights))
+    x2 = x.reshape(-1, K)
+    if not _fused_ok(x2, weights):
+        return _grouped_composition(x, weights, splits, slabs)
+    with torch.no_grad():
+        ys = native.C().linear_fp8_grouped(x2, [c for c, _ in weights], [s for _, s in weights],
+                                           0 if splits is None else max(int(splits), 1),
+                                           0 if slabs is None else max(int(slabs), 1))
+    return tuple(y.view(*x.shape[:-1], y.shape[1]) for y in ys)
+
+
+def swiglu_linear_fp8(x: torch.Tensor, gate_codes: torch.Tensor, gate_scale: torch.Tensor, up_codes: torch.Tensor,
+                      up_scale: torch.Tensor, splits: Optional[int] = None, slabs: Optional[int] = None) -> torch.Tensor:
+    """``ops.lm.swiglu(linear_fp8(x, gate), linear_fp8(x, up))`` for two weights ``[N, K]``. When both pass
+    ``linear_fp8_native_ok`` one launch of the gfx950 kernel computes it (and one combine, when K is split): a
+    workgroup owns 16 gate channels and the same 16 up channels, rounds both sums to bf16 as the separate calls
+    would and applies SwiGLU in its epilogue, so neither ``[M, N]`` intermediate is written or read and the bits
+    are the composition's at the same ``slabs`` (``None``: ``swiglu_linear_fp8_splits``). Anything else is that
+    composition."""
+    if gate_codes.dim() != 2 or gate_codes.shape != up_codes.shape or gate_codes.shape[1] != x.shape[-1]:
+        raise ValueError(f"swiglu_linear_fp8: gate {tuple(gate_codes.shape)} and up {tuple(up_codes.shape)} must be one "
+                         f"shape [N, {x.shape[-1]}]")
+    if gate_scale.shape != gate_codes.shape[:1] or up_scale.shape != up_codes.shape[:1]:
+        raise ValueError("swiglu_linear_fp8: a scale must be [N]")
+    _no_grad_inputs("swiglu_linear_fp8", x, gate_scale, up_scale)
+    x2 = x.reshape(-1, x.shape[-1])
+    if not _fused_ok(x2, ((gate_codes, gate_scale), (up_codes, up_scale))):
+        return _swiglu_composition(x, gate_codes, gate_scale, up_codes, up_scale, splits, slabs)
+    with torch.no_grad():
+        y = native.C().swiglu_linear_fp8(x2, gate_codes, gate_scale, up_codes, up_scale,
+                                         0 if splits is None else max(int(splits), 1),
+                                         0 if slabs is None else max(int(slabs), 1))
+    return y.view(*x.shape[:-1], gate_codes.shape[0])
+
+
+def autocast_input(x: torch.Tensor) -> torch.Tensor:
+    """``x`` as an ``Fp8Linear`` reads it: cast to bf16 under bf16 GPU autocast, untouched otherwise"""
+    if x.is_cuda and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16:
+        return x.to(torch.bfloat16)
+    return x
+
+
 class Fp8Linear(torch.nn.Module):
     """A bias-free projection whose weight is FP8 codes (buffer ``weight`` ``[out, in]``) and per-channel scales
     (buffer ``weight_scale`` ``[out]``). Inference only: an input that requires grad raises. Under bf16 GPU
@@ -123,9 +206,7 @@ class Fp8Linear(torch.nn.Module):
         return m
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if x.is_cuda and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16:
-            x = x.to(torch.bfloat16)
-        return linear_fp8(x, self.weight, self.weight_scale)
+        return linear_fp8(autocast_input(x), self.weight, self.weight_scale)
 
     def extra_repr(self) -> str:
         return f"in_features={self.in_features}, out_features={self.out_features}, weight=float8_e4m3fn"

@@ -1008,6 +1008,107 @@ torch::Tensor linear_fp8(torch::Tensor x, torch::Tensor codes, torch::Tensor sca
   return y;
 }
 
+// the checks linear_fp8 makes, for the fused entries below: x bf16 [M, K] with 1 <= M <= linear_fp8_max_m(), one
+// weight (codes [N, K], scale [N]) with N > 0; returns the weight's row stride in bytes
+size_t fp8_fused_weight(const char* fn, const torch::Tensor& x, const torch::Tensor& codes, const torch::Tensor& scale) {
+  TORCH_CHECK(codes.is_cuda() && scale.is_cuda() && codes.device() == x.device() && scale.device() == x.device(), fn,
+              ": all tensors must be on one GPU");
+  TORCH_CHECK(codes.scalar_type() == at::kFloat8_e4m3fn && scale.scalar_type() == at::kFloat, fn,
+              ": codes must be float8_e4m3fn and scale float32");
+  const int64_t K = x.size(1);
+  TORCH_CHECK(codes.dim() == 2 && scale.dim() == 1 && codes.size(1) == K && scale.size(0) == codes.size(0), fn,
+              ": x [M, K], codes [N, K] and scale [N] must agree");
+  const int64_t N = codes.size(0);
+  TORCH_CHECK(N > 0 && N % 8 == 0 && N <= INT_MAX, fn, ": N must be a positive multiple of 8, got ", N);
+  TORCH_CHECK(codes.stride(1) == 1 && (N == 1 || (codes.stride(0) >= K && codes.stride(0) % 16 == 0)), fn,
+              ": codes need unit inner stride and a row stride >= K that is a multiple of 16");
+  TORCH_CHECK(scale.is_contiguous(), fn, ": scale must be contiguous");
+  check_aligned(codes, "codes"); check_aligned(scale, "scale");
+  return (size_t)codes.stride(0);
+}
+
+void fp8_fused_x(const char* fn, const torch::Tensor& x) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2, fn, ": x must be a bfloat16 GPU tensor [M, K]");
+  const int64_t M = x.size(0), K = x.size(1);
+  TORCH_CHECK(M >= 1 && M <= cs_linear_fp8_max_m(), fn, ": M must be in [1, ", cs_linear_fp8_max_m(), "], got ", M);
+  TORCH_CHECK(K >= 64 && K % 64 == 0 && K <= INT_MAX, fn, ": K must be a positive multiple of 64, got ", K);
+  TORCH_CHECK(x.stride(1) == 1 && (M == 1 || (x.stride(0) >= K && x.stride(0) % 8 == 0)), fn,
+              ": x needs unit inner stride and a row stride >= K that is a multiple of 8");
+  check_aligned(x, "x");
+}
+
+// slabs (0: `dflt`, otherwise clamped into [1, cs_linear_fp8_max_splits(K)]) and the workgroups that share them
+std::pair<int, int> fp8_slabs_wgs(int64_t slabs_arg, int64_t splits, int dflt, int K) {
+  const int slabs = slabs_arg == 0 ? dflt
+                                   : (int)std::min<int64_t>(std::max<int64_t>(slabs_arg, 1), cs_linear_fp8_max_splits(K));
+  return {slabs, splits == 0 ? slabs : (int)std::min<int64_t>(std::max<int64_t>(splits, 1), slabs)};
+}
+
+// grouped FP8 linear (linear_fp8.hip): 1 to linear_fp8_max_group weights that share x, each its own (codes, scale)
+// pair, one launch -> one y_i bf16 [M, N_i] per weight, bit-equal to linear_fp8 at the same `slabs`. slabs 0: the
+// count cs_linear_fp8_grouped_splits picks from the summed tiles. No empty operands: the caller routes those.
+std::vector<torch::Tensor> linear_fp8_grouped(torch::Tensor x, std::vector<torch::Tensor> codes,
+                                              std::vector<torch::Tensor> scales, int64_t splits, int64_t slabs_arg) {
+  const char* fn = "linear_fp8_grouped";
+  const int G = (int)codes.size();
+  TORCH_CHECK(G >= 1 && G <= cs_linear_fp8_max_group() && scales.size() == codes.size(), fn, ": 1 to ",
+              cs_linear_fp8_max_group(), " (codes, scale) pairs, got ", codes.size());
+  fp8_fused_x(fn, x);
+  const int64_t M = x.size(0), K = x.size(1);
+  DevGuard g(x.device());
+  const void* cp[3] = {};
+  const float* sp[3] = {};
+  void* yp[3] = {};
+  int N[3] = {};
+  size_t ldw[3] = {};
+  int64_t Ntot = 0;
+  std::vector<torch::Tensor> ys;
+  for (int i = 0; i < G; ++i) {
+    ldw[i] = fp8_fused_weight(fn, x, codes[i], scales[i]);
+    N[i] = (int)codes[i].size(0);
+    Ntot += N[i];
+    ys.push_back(torch::empty({M, (int64_t)N[i]}, x.options()));
+    check_aligned(ys.back(), "y");
+    cp[i] = codes[i].data_ptr(); sp[i] = scales[i].data_ptr<float>(); yp[i] = ys.back().data_ptr();
+  }
+  TORCH_CHECK(Ntot <= INT_MAX, fn, ": too many output channels");
+  const auto [slabs, wgs] = fp8_slabs_wgs(slabs_arg, splits, cs_linear_fp8_grouped_splits((int)M, N, G, (int)K), (int)K);
+  torch::Tensor ws;
+  float* wsp = nullptr;
+  if (slabs > 1) {
+    ws = torch::empty({(int64_t)cs_linear_fp8_ws_floats((int)M, (int)Ntot, slabs)}, x.options().dtype(at::kFloat));
+    wsp = ws.data_ptr<float>();
+  }
+  CS_LAUNCH(cs_linear_fp8_grouped(x.data_ptr(), cp, sp, yp, N, ldw, G, wsp, (int)M, (int)K,
+                                  (size_t)(M == 1 ? K : x.stride(0)), slabs, wgs, cur_stream()));
+  return ys;
+}
+
+// SwiGLU of two FP8 linears of the same x (linear_fp8.hip): gate and up [N, K] -> bf16 [M, N], bit-equal to
+// swiglu_fwd(linear_fp8(x, gate), linear_fp8(x, up)) at the same `slabs`; neither intermediate is written
+torch::Tensor swiglu_linear_fp8(torch::Tensor x, torch::Tensor gate, torch::Tensor gate_scale, torch::Tensor up,
+                                torch::Tensor up_scale, int64_t splits, int64_t slabs_arg) {
+  const char* fn = "swiglu_linear_fp8";
+  fp8_fused_x(fn, x);
+  const size_t ldg = fp8_fused_weight(fn, x, gate, gate_scale), ldu = fp8_fused_weight(fn, x, up, up_scale);
+  TORCH_CHECK(gate.size(0) == up.size(0), fn, ": gate and up must have the same shape");
+  const int64_t M = x.size(0), K = x.size(1), N = gate.size(0);
+  DevGuard g(x.device());
+  auto y = torch::empty({M, N}, x.options());
+  check_aligned(y, "y");
+  const auto [slabs, wgs] = fp8_slabs_wgs(slabs_arg, splits, cs_swiglu_linear_fp8_splits((int)M, (int)N, (int)K), (int)K);
+  torch::Tensor ws;
+  float* wsp = nullptr;
+  if (slabs > 1) {
+    ws = torch::empty({(int64_t)cs_swiglu_linear_fp8_ws_floats((int)M, (int)N, slabs)}, x.options().dtype(at::kFloat));
+    wsp = ws.data_ptr<float>();
+  }
+  CS_LAUNCH(cs_swiglu_linear_fp8(x.data_ptr(), gate.data_ptr(), gate_scale.data_ptr<float>(), up.data_ptr(),
+                                 up_scale.data_ptr<float>(), y.data_ptr(), wsp, (int)M, (int)N, (int)K,
+                                 (size_t)(M == 1 ? K : x.stride(0)), ldg, ldu, slabs, wgs, cur_stream()));
+  return y;
+}
+
 // y = a @ b (bf16, a [M, K] K-major, b [K, N] with unit stride along K) plus the BatchNorm
 // statistics of y per 256-row tile: {y, tiles [ceil(M / 256), N, 2] = (mean, M2)}
 std::vector<torch::Tensor> mm_bf16_bn_stats(torch::Tensor a, torch::Tensor b) {
@@ -1129,6 +1230,31 @@ void register_lm_ops(pybind11::module& m) {
         }, "the K slabs linear_fp8 sums for these shapes (from M, N, K and the CU count, never from data)", py::arg("M"),
         py::arg("N"), py::arg("K"));
   m.def("linear_fp8_max_m", &cs_linear_fp8_max_m, "the most rows of x the FP8 linear kernel takes");
+  m.def("linear_fp8_grouped", &linear_fp8_grouped,
+        "grouped FP8 linear: x bf16 [M,K] against 1 to 3 weights (codes [N_i,K], scales [N_i]) in one launch -> a list "
+        "of bf16 [M,N_i], bit-equal to linear_fp8 at the same slabs (0: linear_fp8_grouped_splits); splits as there",
+        py::arg("x"), py::arg("codes"), py::arg("scales"), py::arg("splits") = 0, py::arg("slabs") = 0);
+  m.def("swiglu_linear_fp8", &swiglu_linear_fp8,
+        "swiglu(linear_fp8(x, gate), linear_fp8(x, up)) in one launch, both weights [N,K] -> bf16 [M,N]; slabs 0: "
+        "swiglu_linear_fp8_splits(M, N, K); splits as in linear_fp8",
+        py::arg("x"), py::arg("gate_codes"), py::arg("gate_scale"), py::arg("up_codes"), py::arg("up_scale"),
+        py::arg("splits") = 0, py::arg("slabs") = 0);
+  m.def("linear_fp8_grouped_splits", [](int64_t M, std::vector<int64_t> Ns, int64_t K) {
+          TORCH_CHECK(M >= 0 && K >= 0 && M <= INT_MAX && K <= INT_MAX && !Ns.empty() &&
+                          (int)Ns.size() <= cs_linear_fp8_max_group(), "linear_fp8_grouped_splits: sizes out of range");
+          int N[3] = {};
+          for (size_t i = 0; i < Ns.size(); ++i) {
+            TORCH_CHECK(Ns[i] >= 0 && Ns[i] <= INT_MAX, "linear_fp8_grouped_splits: sizes out of range");
+            N[i] = (int)Ns[i];
+          }
+          return cs_linear_fp8_grouped_splits((int)M, N, (int)Ns.size(), (int)K);
+        }, "the K slabs linear_fp8_grouped sums for these shapes (from M, the summed tiles of Ns, K and the CU count)",
+        py::arg("M"), py::arg("Ns"), py::arg("K"));
+  m.def("swiglu_linear_fp8_splits", [](int64_t M, int64_t N, int64_t K) {
+          TORCH_CHECK(M >= 0 && N >= 0 && K >= 0 && M <= INT_MAX && N <= INT_MAX && K <= INT_MAX,
+                      "swiglu_linear_fp8_splits: sizes out of range");
+          return cs_swiglu_linear_fp8_splits((int)M, (int)N, (int)K);
+        }, "the K slabs swiglu_linear_fp8 sums for these shapes", py::arg("M"), py::arg("N"), py::arg("K"));
   m.def("mm_bf16", &mm_bf16, "C = a @ b on the bf16 matrix cores", pybind11::arg("a"), pybind11::arg("b"),
         pybind11::arg("out_f32") = false, pybind11::arg("acc") = c10::nullopt, pybind11::arg("splits") = -1);
   m.def("mm_bf16_bn_stats", &mm_bf16_bn_stats, "a @ b (bf16) plus per-256-row-tile BatchNorm (mean, M2) of the result");

@@ -432,6 +432,25 @@ int cs_linear_fp8_splits(int M, int N, int K);  // the default slab count: from 
 size_t cs_linear_fp8_ws_floats(int M, int N, int slabs);
 hipError_t cs_linear_fp8(const void* x, const void* codes, const float* scale, void* y, float* ws, int M, int N, int K,
                          size_t ldx, size_t ldw, int slabs, int wgs, hipStream_t stream);
+// The same product for G <= cs_linear_fp8_max_group() weights [N_i, K] that share x, in one launch (plus one
+// combine when slabs > 1): y_i[M, N_i] = (x . codes_i^T) * scale_i. The arrays have G entries; every N_i is a
+// positive multiple of 8, every ldw_i % 16 == 0 and >= K, every pointer 16-byte aligned; x, M, K, ldx, slabs and wgs
+// as above. ws: cs_linear_fp8_ws_floats(M, sum N_i, slabs) floats. Per output element the summation order is
+// cs_linear_fp8's at the same `slabs`, so the bits are. The default slab count comes from the summed tile pairs.
+int cs_linear_fp8_max_group();
+int cs_linear_fp8_grouped_splits(int M, const int* N, int G, int K);
+hipError_t cs_linear_fp8_grouped(const void* x, const void* const* codes, const float* const* scale, void* const* y,
+                                 const int* N, const size_t* ldw, int G, float* ws, int M, int K, size_t ldx, int slabs,
+                                 int wgs, hipStream_t stream);
+// y[M, N] = swiglu(g, u) with g = bf16((x . gate^T) * gate_scale) and u = bf16((x . up^T) * up_scale), both weights
+// [N, K], in one launch (plus one combine when slabs > 1): bit for bit cs_swiglu_fwd on two cs_linear_fp8 results at
+// the same `slabs`, without either reaching memory. Preconditions as cs_linear_fp8 for each weight.
+// ws: cs_swiglu_linear_fp8_ws_floats floats.
+int cs_swiglu_linear_fp8_splits(int M, int N, int K);
+size_t cs_swiglu_linear_fp8_ws_floats(int M, int N, int slabs);
+hipError_t cs_swiglu_linear_fp8(const void* x, const void* gate, const float* gate_scale, const void* up,
+                                const float* up_scale, void* y, float* ws, int M, int N, int K, size_t ldx, size_t ldg,
+                                size_t ldu, int slabs, int wgs, hipStream_t stream);
 
 // decode attention against a KV cache, split over the keys (attn_decode.hip). q / o: bf16 [B, Hq, D]; kc / vc:
 // bf16 [B, Smax, Hkv, D] with row stride Hkv * D and batch stride `batch_stride` elements (% 8 == 0, so a
