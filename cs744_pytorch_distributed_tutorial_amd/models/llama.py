@@ -112,9 +112,11 @@ class Attention(nn.Module):
         """The projections of ``x`` [B, S, dim] as [B, S, H, hd], q and k after (QK-norm and) RoPE with the
         table rows ``cos`` / ``sin`` [S, hd/2]: row s of the tables belongs to position s of the S axis."""
         B, S, _ = x.shape
-        if self.fused_fp8:  # one grouped launch for the three FP8 projections (ops.linear_fp8.linear_fp8_grouped)
+        if self.fused_fp8:  # one grouped launch for the three quantised projections, FP8 or MXFP4 by their type
             from ..ops.linear_fp8 import autocast_input, linear_fp8_grouped
-            q, k, v = linear_fp8_grouped(autocast_input(x), [(w.weight, w.weight_scale) for w in (self.wq, self.wk, self.wv)])
+            from ..ops.linear_mxfp4 import Mxfp4Linear, linear_mxfp4_grouped
+            grouped = linear_mxfp4_grouped if isinstance(self.wq, Mxfp4Linear) else linear_fp8_grouped
+            q, k, v = grouped(autocast_input(x), [(w.weight, w.weight_scale) for w in (self.wq, self.wk, self.wv)])
         else:
             q, k, v = self.wq(x), self.wk(x), self.wv(x)
         q, k, v = q.view(B, S, self.nh, self.hd), k.view(B, S, self.nkv, self.hd), v.view(B, S, self.nkv, self.hd)
@@ -234,10 +236,12 @@ class FeedForward(nn.Module):
         self.fused_fp8 = False  # set by Llama.quantize_weights_(fused=True)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if self.fused_fp8:  # gate, up and SwiGLU in one launch (ops.linear_fp8.swiglu_linear_fp8)
+        if self.fused_fp8:  # gate, up and SwiGLU in one launch, FP8 or MXFP4 by the projections' type
             from ..ops.linear_fp8 import autocast_input, swiglu_linear_fp8
-            return self.w2(swiglu_linear_fp8(autocast_input(x), self.w1.weight, self.w1.weight_scale, self.w3.weight,
-                                             self.w3.weight_scale))
+            from ..ops.linear_mxfp4 import Mxfp4Linear, swiglu_linear_mxfp4
+            fused = swiglu_linear_mxfp4 if isinstance(self.w1, Mxfp4Linear) else swiglu_linear_fp8
+            return self.w2(fused(autocast_input(x), self.w1.weight, self.w1.weight_scale, self.w3.weight,
+                                 self.w3.weight_scale))
         return self.w2(_ops().swiglu(self.w1(x), self.w3(x)))
 
 
@@ -344,19 +348,30 @@ class Llama(nn.Module):
         ``fused=True`` (opt-in) also makes every block project q, k and v in one grouped launch
         (``ops.linear_fp8.linear_fp8_grouped``) and run gate, up and SwiGLU in one (``swiglu_linear_fp8``): the same
         buffers and ``state_dict``, 4 launches where a decode step made 11, and logits that differ from the
-        separate calls' only as a different K-slab count makes them differ (docs/linear_fp8.md)."""
-        if dtype != "fp8":
-            raise ValueError(f"quantize_weights_: only dtype 'fp8' is supported, got {dtype!r}")
+        separate calls' only as a different K-slab count makes them differ (docs/linear_fp8.md).
+
+        ``dtype="mxfp4"`` swaps the same projections for ``ops.linear_mxfp4.Mxfp4Linear`` instead: e2m1 codes, two per
+        byte, and one e8m0 scale per block of 32 input features (0.53 of the FP8 bytes), on the gfx950 MXFP4 linear
+        kernel, with ``fused=True`` through its grouped and paired calls (docs/linear_mxfp4.md). A model holds one
+        format: quantising to the other one afterwards raises ``ValueError``."""
         from ..ops.linear_fp8 import Fp8Linear
+        from ..ops.linear_mxfp4 import Mxfp4Linear
+        kinds = {"fp8": Fp8Linear, "mxfp4": Mxfp4Linear}
+        if dtype not in kinds:
+            raise ValueError(f"quantize_weights_: only dtype 'fp8' or 'mxfp4' is supported, got {dtype!r}")
+        kind = kinds[dtype]
         owners = [(blk.attention, ("wq", "wk", "wv", "wo")) for blk in self.layers]
         owners += [(blk.feed_forward, ("w1", "w3", "w2")) for blk in self.layers]
         if head:
             owners.append((self, ("output",)))
+        if any(isinstance(getattr(mod, name), tuple(kinds.values())) and not isinstance(getattr(mod, name), kind)
+               for mod, names in owners for name in names):
+            raise ValueError(f"quantize_weights_: the model is already quantised to another format than {dtype!r}")
         for mod, names in owners:
             for name in names:
                 lin = getattr(mod, name)
-                if not isinstance(lin, Fp8Linear):
-                    setattr(mod, name, Fp8Linear.from_linear(lin))
+                if not isinstance(lin, kind):
+                    setattr(mod, name, kind.from_linear(lin))
         for blk in self.layers:
             blk.attention.fused_fp8 = blk.feed_forward.fused_fp8 = bool(fused)
         return self

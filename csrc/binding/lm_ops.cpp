@@ -1109,6 +1109,125 @@ torch::Tensor swiglu_linear_fp8(torch::Tensor x, torch::Tensor gate, torch::Tens
   return y;
 }
 
+// ---- MXFP4 weight-only linear (linear_mxfp4.hip): x bf16 [M, K] with unit inner stride, codes uint8 [N, K / 2]
+// (two e2m1 codes per byte, low nibble first), scales uint8 [N, K / 32] (e8m0) -> bf16 [M, N]. 1 <= M <=
+// linear_mxfp4_max_m(), K % 128 == 0, N a positive multiple of 8; empty operands are routed by the callers.
+
+// the checks on x; returns its row stride in elements
+size_t mxfp4_x(const char* fn, const torch::Tensor& x) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2, fn, ": x must be a bfloat16 GPU tensor [M, K]");
+  const int64_t M = x.size(0), K = x.size(1);
+  TORCH_CHECK(M >= 1 && M <= cs_linear_mxfp4_max_m(), fn, ": M must be in [1, ", cs_linear_mxfp4_max_m(), "], got ", M);
+  TORCH_CHECK(K >= 128 && K % 128 == 0 && K <= INT_MAX, fn, ": K must be a positive multiple of 128, got ", K);
+  TORCH_CHECK(x.stride(1) == 1 && (M == 1 || (x.stride(0) >= K && x.stride(0) % 8 == 0)), fn,
+              ": x needs unit inner stride and a row stride >= K that is a multiple of 8");
+  check_aligned(x, "x");
+  return (size_t)(M == 1 ? K : x.stride(0));
+}
+
+// the checks on one weight; returns the row strides of its codes and scales in bytes
+std::pair<size_t, size_t> mxfp4_weight(const char* fn, const torch::Tensor& x, const torch::Tensor& codes,
+                                       const torch::Tensor& scales) {
+  TORCH_CHECK(codes.is_cuda() && scales.is_cuda() && codes.device() == x.device() && scales.device() == x.device(), fn,
+              ": all tensors must be on one GPU");
+  TORCH_CHECK(codes.scalar_type() == at::kByte && scales.scalar_type() == at::kByte, fn, ": codes and scales must be uint8");
+  const int64_t K = x.size(1);
+  TORCH_CHECK(codes.dim() == 2 && scales.dim() == 2 && codes.size(1) == K / 2 && scales.size(1) == K / 32 &&
+                  scales.size(0) == codes.size(0), fn, ": x [M, K], codes [N, K / 2] and scales [N, K / 32] must agree");
+  const int64_t N = codes.size(0);
+  TORCH_CHECK(N > 0 && N % 8 == 0 && N <= INT_MAX, fn, ": N must be a positive multiple of 8, got ", N);
+  TORCH_CHECK(codes.stride(1) == 1 && codes.stride(0) >= K / 2 && codes.stride(0) % 16 == 0, fn,
+              ": codes need unit inner stride and a row stride >= K / 2 that is a multiple of 16");
+  TORCH_CHECK(scales.stride(1) == 1 && scales.stride(0) >= K / 32, fn,
+              ": scales need unit inner stride and a row stride >= K / 32");
+  check_aligned(codes, "codes"); check_aligned(scales, "scales");
+  return {(size_t)codes.stride(0), (size_t)scales.stride(0)};
+}
+
+// slabs (0: `dflt`, otherwise clamped into [1, cs_linear_mxfp4_max_splits(K)]) and the workgroups that share them
+std::pair<int, int> mxfp4_slabs_wgs(int64_t slabs_arg, int64_t splits, int dflt, int K) {
+  const int slabs = slabs_arg == 0 ? dflt
+                                   : (int)std::min<int64_t>(std::max<int64_t>(slabs_arg, 1), cs_linear_mxfp4_max_splits(K));
+  return {slabs, splits == 0 ? slabs : (int)std::min<int64_t>(std::max<int64_t>(splits, 1), slabs)};
+}
+
+// the fp32 workspace of `floats` floats next to x; an undefined tensor when K is not split
+torch::Tensor mxfp4_ws(const torch::Tensor& x, size_t floats) {
+  return floats == 0 ? torch::Tensor() : torch::empty({(int64_t)floats}, x.options().dtype(at::kFloat));
+}
+
+// the plain product. slabs 0: cs_linear_mxfp4_splits(M, N, K), otherwise clamped into [1, cs_linear_mxfp4_max_splits(K)];
+// splits 0: one workgroup per slab, otherwise clamped into [1, slabs] (no effect on the bits)
+torch::Tensor linear_mxfp4(torch::Tensor x, torch::Tensor codes, torch::Tensor scales, int64_t splits, int64_t slabs_arg) {
+  const char* fn = "linear_mxfp4";
+  const size_t ldx = mxfp4_x(fn, x);
+  const auto [ldw, lds] = mxfp4_weight(fn, x, codes, scales);
+  const int64_t M = x.size(0), K = x.size(1), N = codes.size(0);
+  DevGuard g(x.device());
+  auto y = torch::empty({M, N}, x.options());
+  check_aligned(y, "y");
+  const auto [slabs, wgs] = mxfp4_slabs_wgs(slabs_arg, splits, cs_linear_mxfp4_splits((int)M, (int)N, (int)K), (int)K);
+  auto ws = mxfp4_ws(x, cs_linear_mxfp4_ws_floats((int)M, (int)N, slabs));
+  CS_LAUNCH(cs_linear_mxfp4(x.data_ptr(), codes.data_ptr(), scales.data_ptr(), y.data_ptr(),
+                            ws.defined() ? ws.data_ptr<float>() : nullptr, (int)M, (int)N, (int)K, ldx, ldw, lds, slabs, wgs,
+                            cur_stream()));
+  return y;
+}
+
+// 1 to linear_mxfp4_max_group weights that share x, one launch -> one y_i bf16 [M, N_i] per weight, bit-equal to
+// linear_mxfp4 at the same `slabs`. slabs 0: the count cs_linear_mxfp4_grouped_splits picks from the summed tiles.
+std::vector<torch::Tensor> linear_mxfp4_grouped(torch::Tensor x, std::vector<torch::Tensor> codes,
+                                                std::vector<torch::Tensor> scales, int64_t splits, int64_t slabs_arg) {
+  const char* fn = "linear_mxfp4_grouped";
+  const int G = (int)codes.size();
+  TORCH_CHECK(G >= 1 && G <= cs_linear_mxfp4_max_group() && scales.size() == codes.size(), fn, ": 1 to ",
+              cs_linear_mxfp4_max_group(), " (codes, scales) pairs, got ", codes.size());
+  const size_t ldx = mxfp4_x(fn, x);
+  const int64_t M = x.size(0), K = x.size(1);
+  DevGuard g(x.device());
+  const void* cp[3] = {};
+  const void* sp[3] = {};
+  void* yp[3] = {};
+  int N[3] = {};
+  size_t ldw[3] = {}, lds[3] = {};
+  int64_t Ntot = 0;
+  std::vector<torch::Tensor> ys;
+  for (int i = 0; i < G; ++i) {
+    std::tie(ldw[i], lds[i]) = mxfp4_weight(fn, x, codes[i], scales[i]);
+    N[i] = (int)codes[i].size(0);
+    Ntot += N[i];
+    ys.push_back(torch::empty({M, (int64_t)N[i]}, x.options()));
+    check_aligned(ys.back(), "y");
+    cp[i] = codes[i].data_ptr(); sp[i] = scales[i].data_ptr(); yp[i] = ys.back().data_ptr();
+  }
+  TORCH_CHECK(Ntot <= INT_MAX, fn, ": too many output channels");
+  const auto [slabs, wgs] = mxfp4_slabs_wgs(slabs_arg, splits, cs_linear_mxfp4_grouped_splits((int)M, N, G, (int)K), (int)K);
+  auto ws = mxfp4_ws(x, cs_linear_mxfp4_ws_floats((int)M, (int)Ntot, slabs));
+  CS_LAUNCH(cs_linear_mxfp4_grouped(x.data_ptr(), cp, sp, yp, N, ldw, lds, G, ws.defined() ? ws.data_ptr<float>() : nullptr,
+                                    (int)M, (int)K, ldx, slabs, wgs, cur_stream()));
+  return ys;
+}
+
+// swiglu_fwd(linear_mxfp4(x, gate), linear_mxfp4(x, up)) in one launch, bit-equal at the same `slabs`
+torch::Tensor swiglu_linear_mxfp4(torch::Tensor x, torch::Tensor gate, torch::Tensor gate_scales, torch::Tensor up,
+                                  torch::Tensor up_scales, int64_t splits, int64_t slabs_arg) {
+  const char* fn = "swiglu_linear_mxfp4";
+  const size_t ldx = mxfp4_x(fn, x);
+  const auto [ldg, ldgs] = mxfp4_weight(fn, x, gate, gate_scales);
+  const auto [ldu, ldus] = mxfp4_weight(fn, x, up, up_scales);
+  TORCH_CHECK(gate.size(0) == up.size(0), fn, ": gate and up must have the same shape");
+  const int64_t M = x.size(0), K = x.size(1), N = gate.size(0);
+  DevGuard g(x.device());
+  auto y = torch::empty({M, N}, x.options());
+  check_aligned(y, "y");
+  const auto [slabs, wgs] = mxfp4_slabs_wgs(slabs_arg, splits, cs_swiglu_linear_mxfp4_splits((int)M, (int)N, (int)K), (int)K);
+  auto ws = mxfp4_ws(x, cs_swiglu_linear_mxfp4_ws_floats((int)M, (int)N, slabs));
+  CS_LAUNCH(cs_swiglu_linear_mxfp4(x.data_ptr(), gate.data_ptr(), gate_scales.data_ptr(), up.data_ptr(),
+                                   up_scales.data_ptr(), y.data_ptr(), ws.defined() ? ws.data_ptr<float>() : nullptr,
+                                   (int)M, (int)N, (int)K, ldx, ldg, ldgs, ldu, ldus, slabs, wgs, cur_stream()));
+  return y;
+}
+
 // y = a @ b (bf16, a [M, K] K-major, b [K, N] with unit stride along K) plus the BatchNorm
 // statistics of y per 256-row tile: {y, tiles [ceil(M / 256), N, 2] = (mean, M2)}
 std::vector<torch::Tensor> mm_bf16_bn_stats(torch::Tensor a, torch::Tensor b) {
@@ -1255,6 +1374,36 @@ void register_lm_ops(pybind11::module& m) {
                       "swiglu_linear_fp8_splits: sizes out of range");
           return cs_swiglu_linear_fp8_splits((int)M, (int)N, (int)K);
         }, "the K slabs swiglu_linear_fp8 sums for these shapes", py::arg("M"), py::arg("N"), py::arg("K"));
+  m.def("linear_mxfp4", &linear_mxfp4,
+        "MXFP4 weight-only linear: x bf16 [M,K], codes uint8 [N,K/2] (e2m1, low nibble first), scales uint8 [N,K/32] "
+        "(e8m0) -> bf16 [M,N]; 1 <= M <= linear_mxfp4_max_m(), K % 128 == 0, N % 8 == 0; splits: workgroups sharing the "
+        "K slabs of a channel tile (0: one per slab; no effect on the bits); slabs: the K slabs summed in order (0: "
+        "linear_mxfp4_splits(M, N, K))",
+        py::arg("x"), py::arg("codes"), py::arg("scales"), py::arg("splits") = 0, py::arg("slabs") = 0);
+  m.def("linear_mxfp4_grouped", &linear_mxfp4_grouped,
+        "grouped MXFP4 linear: x bf16 [M,K] against 1 to 3 weights in one launch -> a list of bf16 [M,N_i], bit-equal to "
+        "linear_mxfp4 at the same slabs (0: linear_mxfp4_grouped_splits); splits as there",
+        py::arg("x"), py::arg("codes"), py::arg("scales"), py::arg("splits") = 0, py::arg("slabs") = 0);
+  m.def("swiglu_linear_mxfp4", &swiglu_linear_mxfp4,
+        "swiglu(linear_mxfp4(x, gate), linear_mxfp4(x, up)) in one launch, both weights [N,K] -> bf16 [M,N]; slabs 0: "
+        "swiglu_linear_mxfp4_splits(M, N, K); splits as in linear_mxfp4",
+        py::arg("x"), py::arg("gate_codes"), py::arg("gate_scales"), py::arg("up_codes"), py::arg("up_scales"),
+        py::arg("splits") = 0, py::arg("slabs") = 0);
+  m.def("linear_mxfp4_max_m", &cs_linear_mxfp4_max_m, "the most rows of x the MXFP4 linear kernel takes");
+  m.def("linear_mxfp4_splits", [](int64_t M, std::vector<int64_t> Ns, int64_t K, bool swiglu) {
+          TORCH_CHECK(M >= 0 && K >= 0 && M <= INT_MAX && K <= INT_MAX && !Ns.empty() &&
+                          (int)Ns.size() <= cs_linear_mxfp4_max_group(), "linear_mxfp4_splits: sizes out of range");
+          int N[3] = {};
+          for (size_t i = 0; i < Ns.size(); ++i) {
+            TORCH_CHECK(Ns[i] >= 0 && Ns[i] <= INT_MAX, "linear_mxfp4_splits: sizes out of range");
+            N[i] = (int)Ns[i];
+          }
+          if (swiglu) return cs_swiglu_linear_mxfp4_splits((int)M, N[0], (int)K);
+          return Ns.size() == 1 ? cs_linear_mxfp4_splits((int)M, N[0], (int)K)
+                                : cs_linear_mxfp4_grouped_splits((int)M, N, (int)Ns.size(), (int)K);
+        }, "the K slabs the MXFP4 linear kernel sums by default (from M, the tiles of Ns, K and the CU count, never from "
+        "data): the plain call for one N, the grouped call for several, swiglu_linear_mxfp4 with swiglu=True",
+        py::arg("M"), py::arg("Ns"), py::arg("K"), py::arg("swiglu") = false);
   m.def("mm_bf16", &mm_bf16, "C = a @ b on the bf16 matrix cores", pybind11::arg("a"), pybind11::arg("b"),
         pybind11::arg("out_f32") = false, pybind11::arg("acc") = c10::nullopt, pybind11::arg("splits") = -1);
   m.def("mm_bf16_bn_stats", &mm_bf16_bn_stats, "a @ b (bf16) plus per-256-row-tile BatchNorm (mean, M2) of the result");

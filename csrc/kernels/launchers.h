@@ -451,6 +451,37 @@ size_t cs_swiglu_linear_fp8_ws_floats(int M, int N, int slabs);
 hipError_t cs_swiglu_linear_fp8(const void* x, const void* gate, const float* gate_scale, const void* up,
                                 const float* up_scale, void* y, float* ws, int M, int N, int K, size_t ldx, size_t ldg,
                                 size_t ldu, int slabs, int wgs, hipStream_t stream);
+// MXFP4 weight-only linear for decoding (linear_mxfp4.hip): y[M, N] = x[M, K] . W^T with W[c][k] = e2m1 code k of
+// row c times 2^(scales[c][k / 32] - 127). x bf16 with rows ldx elements apart (% 8 == 0, >= K); codes uint8
+// [N, K / 2], element 2 i in the low nibble of byte i, rows ldw bytes apart (% 16 == 0, >= K / 2); scales uint8
+// [N, K / 32] with rows lds bytes apart (>= K / 32); y bf16 [M, N] contiguous; 0 <= M <= cs_linear_mxfp4_max_m(),
+// K % 128 == 0, N % 8 == 0, x / codes / scales / y 16-byte aligned. slabs, wgs and ws as for cs_linear_fp8, with
+// cs_linear_mxfp4_max_splits and cs_linear_mxfp4_ws_floats. M == 0 or N == 0 launches nothing.
+// hipErrorInvalidValue on anything else.
+int cs_linear_mxfp4_max_m();
+int cs_linear_mxfp4_max_splits(int K);
+int cs_linear_mxfp4_splits(int M, int N, int K);  // the default slab count: from M, N, K and the CU count only
+size_t cs_linear_mxfp4_ws_floats(int M, int N, int slabs);
+hipError_t cs_linear_mxfp4(const void* x, const void* codes, const void* scales, void* y, float* ws, int M, int N, int K,
+                           size_t ldx, size_t ldw, size_t lds, int slabs, int wgs, hipStream_t stream);
+// The same product for G <= cs_linear_mxfp4_max_group() weights [N_i, K] that share x, in one launch of the same
+// kernel (plus one combine when slabs > 1). The arrays have G entries; every N_i is a positive multiple of 8.
+// ws: cs_linear_mxfp4_ws_floats(M, sum N_i, slabs) floats. Per output element the summation order is
+// cs_linear_mxfp4's at the same `slabs`, so the bits are. The default slab count comes from the summed tile pairs.
+int cs_linear_mxfp4_max_group();
+int cs_linear_mxfp4_grouped_splits(int M, const int* N, int G, int K);
+hipError_t cs_linear_mxfp4_grouped(const void* x, const void* const* codes, const void* const* scales, void* const* y,
+                                   const int* N, const size_t* ldw, const size_t* lds, int G, float* ws, int M, int K,
+                                   size_t ldx, int slabs, int wgs, hipStream_t stream);
+// y[M, N] = swiglu(bf16(x . gate^T), bf16(x . up^T)), both weights [N, K], in one launch of the same kernel (plus
+// one combine when slabs > 1): bit for bit cs_swiglu_fwd on two cs_linear_mxfp4 results at the same `slabs`,
+// without either reaching memory. Preconditions as cs_linear_mxfp4 for each weight (ldg / ldu: code rows, ldgs /
+// ldus: scale rows). ws: cs_swiglu_linear_mxfp4_ws_floats floats.
+int cs_swiglu_linear_mxfp4_splits(int M, int N, int K);
+size_t cs_swiglu_linear_mxfp4_ws_floats(int M, int N, int slabs);
+hipError_t cs_swiglu_linear_mxfp4(const void* x, const void* gate, const void* gate_scales, const void* up,
+                                  const void* up_scales, void* y, float* ws, int M, int N, int K, size_t ldx, size_t ldg,
+                                  size_t ldgs, size_t ldu, size_t ldus, int slabs, int wgs, hipStream_t stream);
 
 // decode attention against a KV cache, split over the keys (attn_decode.hip). q / o: bf16 [B, Hq, D]; kc / vc:
 // bf16 [B, Smax, Hkv, D] with row stride Hkv * D and batch stride `batch_stride` elements (% 8 == 0, so a
