@@ -143,7 +143,11 @@ struct OpM {
   template <bool KTAIL>
   __device__ __forceinline__ void stage(char* img, int h, int k0) const {
     const int rows = K - k0 < kBK ? K - k0 : kBK;
-    const int bytes = (int)((int64_t)(rows - 1) * ld * 2 + (int64_t)ncols * 2);
+    // the range check is per dword: with ncols odd (an A operand of odd M; N % 4 == 0 keeps B even)
+    // a range ending on column ncols - 1 of the last k row would cut that column's dword and zero
+    // it, so the range ends on the dword boundary. The extra element is the row's own padding
+    // (ld % 8 == 0 and ld >= M give ld > M) and lands in an output row >= M, never stored.
+    const int bytes = (int)((int64_t)(rows - 1) * ld * 2 + (((int64_t)ncols * 2 + 3) & ~(int64_t)3));
     const __amdgpu_buffer_rsrc_t rs =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(base + (int64_t)k0 * ld), (short)0, bytes, 0x00020000);
 #pragma unroll
