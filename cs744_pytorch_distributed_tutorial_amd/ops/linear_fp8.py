@@ -1,4 +1,5 @@
-"""FP8 weight-only projections for decoding (W8A16): ``csrc/kernels/linear_fp8.hip``.
+"""FP8 weight-only projections (W8A16): ``csrc/kernels/linear_fp8.hip`` for decoding (up to 64 rows) and
+``csrc/kernels/linear_fp8_gemm.hip`` for prefills and larger batches.
 
 A weight ``[N, K]`` is stored as float8_e4m3fn codes plus one power-of-two fp32 scale per output channel, the
 format ``ops.attention.kv_quantize_ref`` defines, applied to the rows of the weight. Every code is exactly a
@@ -67,6 +68,52 @@ def linear_fp8_native_ok(x2: torch.Tensor, codes: torch.Tensor, scale: torch.Ten
     return scale.is_contiguous() and all(t.data_ptr() % 16 == 0 for t in (x2, codes, scale))
 
 
+def linear_fp8_gemm_splits(M: int, N: int, K: int) -> int:
+    """The K slabs the large-M kernel (``linear_fp8_gemm.hip``) cuts K into for these shapes: from M, N, K and the
+    CU count only, never from data, and 1 whenever the fp32 partials would pass 256 MiB."""
+    return native.C().linear_fp8_gemm_splits(M, N, K)
+
+
+# cs_linear_fp8_gemm (csrc/kernels/launchers.h): offsets inside a tile's buffer descriptor are 32-bit. A tile
+# addresses 128 rows, at most 128 * 2 * ldx bytes of x and 128 * ldw bytes of codes, and both stay below 0x7ffffff0
+_GEMM_OOB = 0x7FFFFFF0
+_GEMM_TILE_ROWS = 128
+# The most rows linear_fp8 sends to the GEMM. docs/linear_fp8.md, "Measurements, M > 64": up to 6144 rows the kernel
+# beats the dequantise-and-multiply path on all five Llama-3-8B shapes by more than the run-to-run spread (1.09x to
+# 1.5x at 3072 to 6144 rows); at 8192 rows the slow path wins on 4096 x 4096 (0.97x) and ties on 4096 x 14336, and
+# generate with a prefill of 8192 rows is 1.2 % slower on the kernel. The kernel itself takes any M.
+_GEMM_MAX_M = 6144
+
+
+def _gemm_layout_ok(x2: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor) -> bool:
+    """the host-side arithmetic of ``linear_fp8_gemm_ok``: types, shapes and strides, whatever device holds them"""
+    if x2.dtype != torch.bfloat16 or codes.dtype != FP8 or scale.dtype != torch.float32:
+        return False
+    if x2.dim() != 2 or codes.dim() != 2 or scale.dim() != 1:
+        return False
+    (M, K), N = x2.shape, codes.shape[0]
+    if codes.shape[1] != K or scale.shape[0] != N or not linear_fp8_max_m() < M <= _GEMM_MAX_M or max(N, K) >= 2**31:
+        return False
+    if N == 0:
+        return True  # an empty result, no launch
+    if K < 64 or K % 64 != 0 or N % 8 != 0:
+        return False
+    ldx, ldw = x2.stride(0), codes.stride(0) if N > 1 else K
+    if x2.stride(1) != 1 or ldx < K or ldx % 8 != 0 or codes.stride(1) != 1 or ldw < K or ldw % 16 != 0:
+        return False
+    return _GEMM_TILE_ROWS * 2 * ldx < _GEMM_OOB and _GEMM_TILE_ROWS * ldw < _GEMM_OOB and scale.is_contiguous()
+
+
+def linear_fp8_gemm_ok(x2: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor) -> bool:
+    """Whether ``linear_fp8_gemm_kernel`` takes these operands and ``linear_fp8`` sends them there: the conditions of
+    ``linear_fp8_native_ok`` with ``linear_fp8_max_m()`` < M <= 6144 in place of the cap on M (above 6144 rows the
+    slow path measured no slower: ``_GEMM_MAX_M``), and row strides whose 32-bit offsets fit a tile's buffer
+    descriptor (x up to 8388607 elements, codes up to 16777215 bytes). The tensors themselves may pass 2^31 bytes."""
+    if not (x2.is_cuda and codes.is_cuda and scale.is_cuda and codes.device == x2.device == scale.device):
+        return False
+    return _gemm_layout_ok(x2, codes, scale) and all(t.data_ptr() % 16 == 0 for t in (x2, codes, scale))
+
+
 def _dequant_mm(x2: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     """The slow path on the GPU for bf16 ``x2``: the weight dequantised to bf16 (exact), then the bf16 GEMM"""
     from .lm import _mm
@@ -78,17 +125,22 @@ def linear_fp8(x: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor, splits
                slabs: Optional[int] = None) -> torch.Tensor:
     """``y[..., N] = x[..., K] @ (codes[N, K] * scale[N, None])^T`` in ``x``'s dtype.
 
-    The gfx950 kernel runs when ``linear_fp8_native_ok`` holds for ``x`` flattened to ``[M, K]``: decode steps
-    and short extends (M up to ``linear_fp8_max_m()``). Anything else takes the slow path: on the GPU with a
-    bf16 ``x`` the weight is dequantised to bf16 and multiplied by the bf16 GEMM of ``ops.lm`` (a prefill reads
-    and writes the whole weight once more per call; a kernel for large M is future work), and everywhere else
-    ``linear_fp8_ref`` runs.
+    Two gfx950 kernels serve ``x`` flattened to ``[M, K]``. When ``linear_fp8_native_ok`` holds the skinny kernel
+    runs: decode steps and short extends (M up to ``linear_fp8_max_m()``). Otherwise, when ``linear_fp8_gemm_ok``
+    holds, the LDS-tiled GEMM of ``linear_fp8_gemm.hip`` runs: prefills, chunks of a chunked prefill, long extends
+    and decode batches above ``linear_fp8_max_m()`` and up to 6144 rows; it reads the codes once and never
+    materialises a bf16 weight. Anything else takes the slow path: on the GPU with a bf16 ``x`` the weight is dequantised to bf16 and
+    multiplied by the bf16 GEMM of ``ops.lm``, and everywhere else ``linear_fp8_ref`` runs.
 
-    The kernel cuts K into slabs and sums them in a fixed order. ``slabs`` is their number: ``None`` is
-    ``linear_fp8_splits(M, N, K)``, anything else is clamped into [1, K / 128]; it fixes the summation order and
-    so the last bits of the result. ``splits`` is a workgroup count, not a slab count: how many workgroups share
-    the slabs of a channel tile (``None``: one per slab; otherwise clamped into [1, slabs]). It moves work and
-    changes no bit of the result. Both are ignored off the kernel. Inference only."""
+    Both kernels cut K into slabs and sum them in a fixed order. ``slabs`` is their number; it fixes the summation
+    order and so the last bits of the result. On the skinny kernel ``None`` is ``linear_fp8_splits(M, N, K)`` and
+    anything else is clamped into [1, K / 128]; on the GEMM ``None`` is ``linear_fp8_gemm_splits(M, N, K)`` and
+    anything else is clamped into [1, K / 64], and for a fixed ``slabs`` a row's bits do not depend on M or on where
+    the row stands, so chunking a prefill differently changes nothing. The two kernels sum in different orders:
+    their results agree to rounding, not bit for bit. ``splits`` is a workgroup count of the skinny kernel, not a
+    slab count: how many workgroups share the slabs of a channel tile (``None``: one per slab; otherwise clamped
+    into [1, slabs]). It moves work and changes no bit of the result; the GEMM ignores it. Both are ignored off
+    the kernels. Inference only."""
     _no_grad_inputs("linear_fp8", x, scale)
     K = x.shape[-1]
     x2 = x.reshape(-1, K)
@@ -96,6 +148,9 @@ def linear_fp8(x: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor, splits
         with torch.no_grad():
             y = native.C().linear_fp8(x2, codes, scale, 0 if splits is None else max(int(splits), 1),
                                       0 if slabs is None else max(int(slabs), 1))
+    elif linear_fp8_gemm_ok(x2, codes, scale):
+        with torch.no_grad():
+            y = native.C().linear_fp8_gemm(x2, codes, scale, 0 if slabs is None else max(int(slabs), 1))
     elif x2.is_cuda and x2.dtype == torch.bfloat16 and codes.is_cuda:
         y = _dequant_mm(x2, codes, scale)
     else:

@@ -1008,6 +1008,51 @@ torch::Tensor linear_fp8(torch::Tensor x, torch::Tensor codes, torch::Tensor sca
   return y;
 }
 
+// FP8 weight-only GEMM (linear_fp8_gemm.hip): the operands and checks of linear_fp8 without the cap on M, for the
+// prefill and batches over linear_fp8_max_m() rows. K is summed in `slabs` runs of 64-wide K-tiles (0 =
+// cs_linear_fp8_gemm_splits(M, N, K), otherwise clamped into [1, cs_linear_fp8_gemm_max_splits(K)]); for a fixed
+// slab count a row's bits do not depend on M. Row strides past the 32-bit offsets of a tile's buffer descriptor
+// are refused. An empty x or weight gives an empty y whatever K and N are.
+torch::Tensor linear_fp8_gemm(torch::Tensor x, torch::Tensor codes, torch::Tensor scale, int64_t slabs_arg) {
+  for (auto* t : {&x, &codes, &scale}) TORCH_CHECK(t->is_cuda(), "linear_fp8_gemm: all tensors must be GPU tensors");
+  TORCH_CHECK(codes.device() == x.device() && scale.device() == x.device(),
+              "linear_fp8_gemm: all tensors must be on one device");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "linear_fp8_gemm: x must be bfloat16");
+  TORCH_CHECK(codes.scalar_type() == at::kFloat8_e4m3fn, "linear_fp8_gemm: codes must be float8_e4m3fn");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat, "linear_fp8_gemm: scale must be float32");
+  TORCH_CHECK(x.dim() == 2 && codes.dim() == 2 && scale.dim() == 1, "linear_fp8_gemm: x [M, K], codes [N, K], scale [N]");
+  const int64_t M = x.size(0), K = x.size(1), N = codes.size(0);
+  TORCH_CHECK(codes.size(1) == K && scale.size(0) == N,
+              "linear_fp8_gemm: x [M, K], codes [N, K] and scale [N] must agree");
+  DevGuard g(x.device());
+  auto y = torch::empty({M, N}, x.options());
+  if (M == 0 || N == 0) return y;
+  TORCH_CHECK(M <= INT_MAX, "linear_fp8_gemm: M out of range, got ", M);
+  TORCH_CHECK(K >= 64 && K % 64 == 0 && K <= INT_MAX, "linear_fp8_gemm: K must be a positive multiple of 64, got ", K);
+  TORCH_CHECK(N % 8 == 0 && N <= INT_MAX, "linear_fp8_gemm: N must be a multiple of 8, got ", N);
+  const int64_t ldx = M == 1 ? K : x.stride(0), ldw = N == 1 ? K : codes.stride(0);
+  TORCH_CHECK(x.stride(1) == 1 && ldx >= K && ldx % 8 == 0 && ldx <= cs_linear_fp8_gemm_max_ldx(),
+              "linear_fp8_gemm: x needs unit inner stride and a row stride >= K that is a multiple of 8 and at most ",
+              cs_linear_fp8_gemm_max_ldx());
+  TORCH_CHECK(codes.stride(1) == 1 && ldw >= K && ldw % 16 == 0 && ldw <= cs_linear_fp8_gemm_max_ldw(),
+              "linear_fp8_gemm: codes need unit inner stride and a row stride >= K that is a multiple of 16 and at most ",
+              cs_linear_fp8_gemm_max_ldw());
+  TORCH_CHECK(scale.is_contiguous(), "linear_fp8_gemm: scale must be contiguous");
+  check_aligned(x, "x"); check_aligned(codes, "codes"); check_aligned(scale, "scale"); check_aligned(y, "y");
+  const int slabs = slabs_arg == 0 ? cs_linear_fp8_gemm_splits((int)M, (int)N, (int)K)
+                                  : (int)std::min<int64_t>(std::max<int64_t>(slabs_arg, 1),
+                                                           cs_linear_fp8_gemm_max_splits((int)K));
+  torch::Tensor ws;
+  float* wsp = nullptr;
+  if (slabs > 1) {
+    ws = torch::empty({(int64_t)cs_linear_fp8_ws_floats((int)M, (int)N, slabs)}, x.options().dtype(at::kFloat));
+    wsp = ws.data_ptr<float>();
+  }
+  CS_LAUNCH(cs_linear_fp8_gemm(x.data_ptr(), codes.data_ptr(), scale.data_ptr<float>(), y.data_ptr(), wsp, (int)M, (int)N,
+                               (int)K, (size_t)ldx, (size_t)ldw, slabs, cur_stream()));
+  return y;
+}
+
 // the checks linear_fp8 makes, for the fused entries below: x bf16 [M, K] with 1 <= M <= linear_fp8_max_m(), one
 // weight (codes [N, K], scale [N]) with N > 0; returns the weight's row stride in bytes
 size_t fp8_fused_weight(const char* fn, const torch::Tensor& x, const torch::Tensor& codes, const torch::Tensor& scale) {
@@ -1349,6 +1394,16 @@ void register_lm_ops(pybind11::module& m) {
         }, "the K slabs linear_fp8 sums for these shapes (from M, N, K and the CU count, never from data)", py::arg("M"),
         py::arg("N"), py::arg("K"));
   m.def("linear_fp8_max_m", &cs_linear_fp8_max_m, "the most rows of x the FP8 linear kernel takes");
+  m.def("linear_fp8_gemm", &linear_fp8_gemm,
+        "FP8 weight-only GEMM for any M >= 1: x bf16 [M,K], codes float8_e4m3fn [N,K], scale fp32 [N] -> bf16 [M,N]; "
+        "K % 64 == 0, N % 8 == 0; slabs: the runs of K-tiles summed in order (0: linear_fp8_gemm_splits(M, N, K))",
+        py::arg("x"), py::arg("codes"), py::arg("scale"), py::arg("slabs") = 0);
+  m.def("linear_fp8_gemm_splits", [](int64_t M, int64_t N, int64_t K) {
+          TORCH_CHECK(M >= 0 && N >= 0 && K >= 0 && M <= INT_MAX && N <= INT_MAX && K <= INT_MAX,
+                      "linear_fp8_gemm_splits: sizes out of range");
+          return cs_linear_fp8_gemm_splits((int)M, (int)N, (int)K);
+        }, "the K slabs linear_fp8_gemm sums for these shapes (from M, N, K and the CU count, never from data)",
+        py::arg("M"), py::arg("N"), py::arg("K"));
   m.def("linear_fp8_grouped", &linear_fp8_grouped,
         "grouped FP8 linear: x bf16 [M,K] against 1 to 3 weights (codes [N_i,K], scales [N_i]) in one launch -> a list "
         "of bf16 [M,N_i], bit-equal to linear_fp8 at the same slabs (0: linear_fp8_grouped_splits); splits as there",

@@ -451,6 +451,30 @@ size_t cs_swiglu_linear_fp8_ws_floats(int M, int N, int slabs);
 hipError_t cs_swiglu_linear_fp8(const void* x, const void* gate, const float* gate_scale, const void* up,
                                 const float* up_scale, void* y, float* ws, int M, int N, int K, size_t ldx, size_t ldg,
                                 size_t ldu, int slabs, int wgs, hipStream_t stream);
+// y[M, N] = bf16((ws[0] + ws[1] + ... + ws[slabs - 1]) * scale[N]) for fp32 partials ws[slabs][M][N], summed in slab
+// order: linear_fp8_combine_kernel, the combine of cs_linear_fp8 and of cs_linear_fp8_gemm. N % 8 == 0; ws, scale
+// and y 16-byte aligned. M == 0 or N == 0 launches nothing.
+hipError_t cs_linear_fp8_combine(const float* ws, const float* scale, void* y, int M, int N, int slabs,
+                                 hipStream_t stream);
+// The same product for any M >= 1 on an LDS-tiled matrix-core GEMM (linear_fp8_gemm.hip): the prefill and batches
+// over cs_linear_fp8_max_m() rows. Operands, alignment, K % 64 == 0 and N % 8 == 0 as for cs_linear_fp8. K is
+// summed in `slabs` contiguous runs of 64-wide K-tiles, 1 <= slabs <= cs_linear_fp8_gemm_max_splits(K) =
+// min(K / 64, 65535), combined in slab order by cs_linear_fp8_combine (no atomics); ws: cs_linear_fp8_ws_floats(M, N,
+// slabs) floats, 16-byte aligned (may be null when slabs == 1). For a fixed `slabs` the summation order of an
+// element depends on K and `slabs` alone, so a row's bits do not depend on M or on the row's position.
+// Index width: the per-tile bases of x, codes, y and ws are 64-bit, so each tensor may pass 2^31 bytes. Inside a
+// tile's buffer descriptor offsets are 32-bit: a tile addresses 128 rows of x and 128 of the codes, at most
+// 128 * ldx * 2 and 128 * ldw bytes, and both must stay below 0x7ffffff0 (the offset that marks a row outside the
+// operand): ldx <= cs_linear_fp8_gemm_max_ldx() = 8388607 elements, ldw <= cs_linear_fp8_gemm_max_ldw() = 16777215
+// bytes. ceil(M / 128) * ceil(N / 128) <= INT_MAX. M == 0 or N == 0 launches nothing. hipErrorInvalidValue on
+// anything else.
+int cs_linear_fp8_gemm_max_splits(int K);
+int64_t cs_linear_fp8_gemm_max_ldx();
+int64_t cs_linear_fp8_gemm_max_ldw();
+// the default slab count: from M, N, K and the CU count only; 1 whenever the partials would pass 256 MiB
+int cs_linear_fp8_gemm_splits(int M, int N, int K);
+hipError_t cs_linear_fp8_gemm(const void* x, const void* codes, const float* scale, void* y, float* ws, int M, int N,
+                              int K, size_t ldx, size_t ldw, int slabs, hipStream_t stream);
 // MXFP4 weight-only linear for decoding (linear_mxfp4.hip): y[M, N] = x[M, K] . W^T with W[c][k] = e2m1 code k of
 // row c times 2^(scales[c][k / 32] - 127). x bf16 with rows ldx elements apart (% 8 == 0, >= K); codes uint8
 // [N, K / 2], element 2 i in the low nibble of byte i, rows ldw bytes apart (% 16 == 0, >= K / 2); scales uint8

@@ -45,6 +45,7 @@
 // register by one v_perm_b32. NaN codes (0x7f, 0xff) are not produced by the quantiser; they give NaN or Inf in
 // the channel's outputs and touch no address.
 #include "common.h"
+#include "fp8_dequant_device.h"
 #include "launchers.h"
 
 namespace {
@@ -52,7 +53,6 @@ namespace {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kKC = 64;         // K per chunk: 16 bytes of a channel in each of the four lane groups
 constexpr int kWaves = 4;       // waves per workgroup, interleaved over the chunks of a slab
@@ -63,20 +63,7 @@ constexpr int kMinChunks = 2;   // chunks per slab the heuristic keeps
 constexpr int kMaxSlabs = 64;
 constexpr int kMaxGroup = 3;    // weights of one grouped launch (q, k and v)
 
-// eight e4m3fn codes (two registers) -> eight bf16 values in k order
-__device__ __forceinline__ bf16x8 dequant8(unsigned lo, unsigned hi) {
-  u32x4 r;
-  const unsigned w[2] = {lo, hi};
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false);  // bytes 0, 1
-    const auto b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);   // bytes 2, 3
-    // the upper halves of two fp32 values, the first in the low half
-    r[2 * i] = __builtin_amdgcn_perm(__float_as_uint(a[1]), __float_as_uint(a[0]), 0x07060302u);
-    r[2 * i + 1] = __builtin_amdgcn_perm(__float_as_uint(b[1]), __float_as_uint(b[0]), 0x07060302u);
-  }
-  return __builtin_bit_cast(bf16x8, r);
-}
+using cs::dequant8;  // eight e4m3fn codes (two registers) -> eight bf16 values in k order (fp8_dequant_device.h)
 
 // the chunks [c0, c1) of part i when n chunks are divided as evenly as possible into parts
 __device__ __forceinline__ void even_part(int n, int parts, int i, int& c0, int& c1) {
@@ -507,6 +494,18 @@ hipError_t cs_linear_fp8(const void* x, const void* codes, const float* scale, v
   const size_t MN = (size_t)M * N;
   hipLaunchKernelGGL(linear_fp8_combine_kernel, dim3((unsigned)((MN / 4 + 255) / 256)), dim3(256), 0, stream, ws, scale,
                      (__bf16*)y, MN, N, slabs);
+  return hipGetLastError();
+}
+
+hipError_t cs_linear_fp8_combine(const float* ws, const float* scale, void* y, int M, int N, int slabs,
+                                 hipStream_t stream) {
+  if (M == 0 || N == 0) return hipSuccess;
+  if (M < 0 || N < 0 || N % 8 != 0 || slabs < 1) return hipErrorInvalidValue;
+  if (!aligned16(ws) || !aligned16(scale) || !aligned16(y)) return hipErrorInvalidValue;
+  const size_t MN = (size_t)M * N, blocks = (MN / 4 + 255) / 256;
+  if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(linear_fp8_combine_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, ws, scale, (__bf16*)y, MN,
+                     N, slabs);
   return hipGetLastError();
 }
 
