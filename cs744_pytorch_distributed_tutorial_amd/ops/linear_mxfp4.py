@@ -1,4 +1,5 @@
-"""MXFP4 weight-only projections for decoding (W4A16): ``csrc/kernels/linear_mxfp4.hip``.
+"""MXFP4 weight-only projections (W4A16): ``csrc/kernels/linear_mxfp4.hip`` for decoding (up to 64 rows) and
+``csrc/kernels/linear_mxfp4_gemm.hip`` for prefills and larger batches.
 
 A weight ``[N, K]`` is stored in the OCP microscaling format: ``codes`` uint8 ``[N, K/2]``, two e2m1 codes per byte
 (element ``2i`` in the low nibble, ``2i+1`` in the high one; values +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}), and ``scales``
@@ -110,6 +111,59 @@ def linear_mxfp4_native_ok(x2: torch.Tensor, codes: torch.Tensor, scales: torch.
     return all(t.data_ptr() % 16 == 0 for t in (x2, codes, scales))
 
 
+def linear_mxfp4_gemm_splits(M: int, N: int, K: int) -> int:
+    """The K slabs the large-M kernel (``linear_mxfp4_gemm.hip``) cuts K into for these shapes: from M, N, K and the
+    CU count only, never from data, and 1 whenever the fp32 partials would pass 256 MiB."""
+    return native.C().linear_mxfp4_gemm_splits(M, N, K)
+
+
+# cs_linear_mxfp4_gemm (csrc/kernels/launchers.h): offsets inside a tile's buffer descriptor are 32-bit. A tile
+# addresses 128 rows, at most 128 * 2 * ldx bytes of x, 128 * ldw of codes and 128 * lds of scales, all below 0x7ffffff0
+_GEMM_OOB = 0x7FFFFFF0
+_GEMM_TILE_ROWS = 128
+# The most rows linear_mxfp4 sends to the GEMM: no cap. docs/linear_mxfp4.md, "Measurements, M > 64": from 64 to 8192
+# rows the kernel beats the dequantise-and-multiply path on all five Llama-3-8B shapes (1.31x at worst, 4096 x 14336
+# at 8192 rows) where the two runs differ by 1 % there and 7 % at most
+_GEMM_MAX_M = 2**31 - 1
+
+
+def _gemm_layout_ok(x2: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor) -> bool:
+    """the host-side arithmetic of ``linear_mxfp4_gemm_ok``: types, shapes and strides, whatever device holds them"""
+    if x2.dtype != torch.bfloat16 or codes.dtype != torch.uint8 or scales.dtype != torch.uint8:
+        return False
+    if x2.dim() != 2 or codes.dim() != 2 or scales.dim() != 2:
+        return False
+    (M, K), N = x2.shape, codes.shape[0]
+    if K % BLOCK != 0 or codes.shape[1] * 2 != K or scales.shape != (N, K // BLOCK) or max(N, K) >= 2**31:
+        return False
+    if not linear_mxfp4_max_m() < M <= _GEMM_MAX_M:
+        return False
+    if N == 0:
+        return True  # an empty result, no launch
+    if K < 128 or K % 128 != 0 or N % 8 != 0:
+        return False
+    ldx = x2.stride(0)
+    ldw, lds = (codes.stride(0), scales.stride(0)) if N > 1 else (K // 2, K // BLOCK)
+    if x2.stride(1) != 1 or ldx < K or ldx % 8 != 0 or codes.stride(1) != 1 or ldw < K // 2 or ldw % 16 != 0:
+        return False
+    if scales.stride(1) != 1 or lds < K // BLOCK or lds % 4 != 0:
+        return False
+    return max(2 * ldx, ldw, lds) * _GEMM_TILE_ROWS < _GEMM_OOB
+
+
+def linear_mxfp4_gemm_ok(x2: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor) -> bool:
+    """Whether ``linear_mxfp4_gemm_kernel`` takes these operands and ``linear_mxfp4`` sends them there: the
+    conditions of ``linear_mxfp4_native_ok`` with M above ``linear_mxfp4_max_m()`` in place of the cap on M, scale
+    rows a multiple of 4 bytes apart from a 4-byte aligned base (they are staged four bytes at a time), and row
+    strides whose 32-bit offsets fit a tile's buffer descriptor (x up to 8388607 elements, codes and scales up to
+    16777215 bytes). The tensors themselves may pass 2^31 bytes."""
+    if not (x2.is_cuda and codes.is_cuda and scales.is_cuda and codes.device == x2.device == scales.device):
+        return False
+    if not _gemm_layout_ok(x2, codes, scales):
+        return False
+    return x2.data_ptr() % 16 == 0 and codes.data_ptr() % 16 == 0 and scales.data_ptr() % 4 == 0
+
+
 def _dequant_mm(x2: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
     """The slow path on the GPU for bf16 ``x2``: the weight dequantised to bf16 (exact), then the bf16 GEMM"""
     from .lm import _mm
@@ -131,15 +185,22 @@ def linear_mxfp4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, spl
                  slabs: Optional[int] = None) -> torch.Tensor:
     """``y[..., N] = x[..., K] @ dequantize_mxfp4(codes, scales)^T`` in ``x``'s dtype.
 
-    The gfx950 kernel runs when ``linear_mxfp4_native_ok`` holds for ``x`` flattened to ``[M, K]``: decode steps and
-    short extends (M up to ``linear_mxfp4_max_m()``). Anything else takes the slow path: on the GPU with a bf16 ``x``
-    the weight is dequantised to bf16 and multiplied by the bf16 GEMM of ``ops.lm``, and everywhere else
-    ``linear_mxfp4_ref`` runs.
+    Two gfx950 kernels serve ``x`` flattened to ``[M, K]``. When ``linear_mxfp4_native_ok`` holds the skinny kernel
+    runs: decode steps and short extends (M up to ``linear_mxfp4_max_m()``). Otherwise, when
+    ``linear_mxfp4_gemm_ok`` holds, the LDS-tiled GEMM of ``linear_mxfp4_gemm.hip`` runs: prefills, chunks of a
+    chunked prefill, long extends and decode batches above ``linear_mxfp4_max_m()`` rows; it reads the codes once
+    and never materialises a bf16 weight. Anything else takes the slow path: on the GPU with a bf16 ``x`` the weight
+    is dequantised to bf16 and multiplied by the bf16 GEMM of ``ops.lm``, and everywhere else ``linear_mxfp4_ref``
+    runs.
 
-    ``slabs`` (``None``: ``linear_mxfp4_splits(M, N, K)``, otherwise clamped into [1, K / 256]) is the number of K
-    slabs the kernel sums in a fixed order: it fixes the last bits of the result. ``splits`` is how many workgroups
+    Both kernels cut K into slabs and sum them in a fixed order. ``slabs`` is their number; it fixes the summation
+    order and so the last bits of the result. On the skinny kernel ``None`` is ``linear_mxfp4_splits(M, N, K)`` and
+    anything else is clamped into [1, K / 256]; on the GEMM ``None`` is ``linear_mxfp4_gemm_splits(M, N, K)`` and
+    anything else is clamped into [1, K / 128], and for a fixed ``slabs`` a row's bits do not depend on M or on
+    where the row stands, so chunking a prefill differently changes nothing. The two kernels sum in different
+    orders: their results agree to rounding, not bit for bit. ``splits`` is how many workgroups of the skinny kernel
     share the slabs of a channel tile (``None``: one per slab; otherwise clamped into [1, slabs]); it moves work
-    and changes no bit. Both are ignored off the kernel. Inference only."""
+    and changes no bit, and the GEMM ignores it. Both are ignored off the kernels. Inference only."""
     _check_weight("linear_mxfp4", x.shape[-1], codes, scales)
     _no_grad_inputs("linear_mxfp4", x)
     x2 = x.reshape(-1, x.shape[-1])
@@ -149,6 +210,9 @@ def linear_mxfp4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, spl
         else:
             with torch.no_grad():
                 y = native.C().linear_mxfp4(x2, codes, scales, _arg(splits), _arg(slabs))
+    elif linear_mxfp4_gemm_ok(x2, codes, scales):
+        with torch.no_grad():
+            y = native.C().linear_mxfp4_gemm(x2, codes, scales, _arg(slabs))
     elif x2.is_cuda and x2.dtype == torch.bfloat16 and codes.is_cuda:
         y = _dequant_mm(x2, codes, scales)
     else:

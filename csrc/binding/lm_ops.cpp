@@ -1273,6 +1273,51 @@ torch::Tensor swiglu_linear_mxfp4(torch::Tensor x, torch::Tensor gate, torch::Te
   return y;
 }
 
+// MXFP4 weight-only GEMM (linear_mxfp4_gemm.hip): the operands and checks of linear_mxfp4 without the cap on M, for
+// the prefill and batches over linear_mxfp4_max_m() rows; the scale rows must also be 4 bytes apart in multiples of
+// 4 from a 4-byte aligned base. K is summed in `slabs` runs of 128-k chunks (0 = cs_linear_mxfp4_gemm_splits(M, N,
+// K), otherwise clamped into [1, cs_linear_mxfp4_gemm_max_splits(K)]); for a fixed slab count a row's bits do not
+// depend on M. Row strides past the 32-bit offsets of a tile's buffer descriptor are refused. An empty x or weight
+// gives an empty y whatever K and N are.
+torch::Tensor linear_mxfp4_gemm(torch::Tensor x, torch::Tensor codes, torch::Tensor scales, int64_t slabs_arg) {
+  const char* fn = "linear_mxfp4_gemm";
+  for (auto* t : {&x, &codes, &scales}) TORCH_CHECK(t->is_cuda(), fn, ": all tensors must be GPU tensors");
+  TORCH_CHECK(codes.device() == x.device() && scales.device() == x.device(), fn, ": all tensors must be on one device");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, fn, ": x must be bfloat16");
+  TORCH_CHECK(codes.scalar_type() == at::kByte && scales.scalar_type() == at::kByte, fn, ": codes and scales must be uint8");
+  TORCH_CHECK(x.dim() == 2 && codes.dim() == 2 && scales.dim() == 2, fn, ": x [M, K], codes [N, K / 2], scales [N, K / 32]");
+  const int64_t M = x.size(0), K = x.size(1), N = codes.size(0);
+  TORCH_CHECK(K % 32 == 0 && codes.size(1) == K / 2 && scales.size(0) == N && scales.size(1) == K / 32, fn,
+              ": x [M, K], codes [N, K / 2] and scales [N, K / 32] must agree");
+  DevGuard g(x.device());
+  auto y = torch::empty({M, N}, x.options());
+  if (M == 0 || N == 0) return y;
+  TORCH_CHECK(M <= INT_MAX, fn, ": M out of range, got ", M);
+  TORCH_CHECK(K >= 128 && K % 128 == 0 && K <= INT_MAX, fn, ": K must be a positive multiple of 128, got ", K);
+  TORCH_CHECK(N % 8 == 0 && N <= INT_MAX, fn, ": N must be a multiple of 8, got ", N);
+  const int64_t ldx = M == 1 ? K : x.stride(0), ldw = N == 1 ? K / 2 : codes.stride(0),
+                lds = N == 1 ? K / 32 : scales.stride(0);
+  TORCH_CHECK(x.stride(1) == 1 && ldx >= K && ldx % 8 == 0 && ldx <= cs_linear_mxfp4_gemm_max_ldx(), fn,
+              ": x needs unit inner stride and a row stride >= K that is a multiple of 8 and at most ",
+              cs_linear_mxfp4_gemm_max_ldx());
+  TORCH_CHECK(codes.stride(1) == 1 && ldw >= K / 2 && ldw % 16 == 0 && ldw <= cs_linear_mxfp4_gemm_max_ldw(), fn,
+              ": codes need unit inner stride and a row stride >= K / 2 that is a multiple of 16 and at most ",
+              cs_linear_mxfp4_gemm_max_ldw());
+  TORCH_CHECK(scales.stride(1) == 1 && lds >= K / 32 && lds % 4 == 0 && lds <= cs_linear_mxfp4_gemm_max_lds(), fn,
+              ": scales need unit inner stride and a row stride >= K / 32 that is a multiple of 4 and at most ",
+              cs_linear_mxfp4_gemm_max_lds());
+  check_aligned(x, "x"); check_aligned(codes, "codes"); check_aligned(y, "y");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(scales.data_ptr()) % 4 == 0, "scales must be 4-byte aligned");
+  const int slabs = slabs_arg == 0 ? cs_linear_mxfp4_gemm_splits((int)M, (int)N, (int)K)
+                                  : (int)std::min<int64_t>(std::max<int64_t>(slabs_arg, 1),
+                                                           cs_linear_mxfp4_gemm_max_splits((int)K));
+  auto ws = mxfp4_ws(x, slabs > 1 ? cs_linear_mxfp4_ws_floats((int)M, (int)N, slabs) : 0);
+  CS_LAUNCH(cs_linear_mxfp4_gemm(x.data_ptr(), codes.data_ptr(), scales.data_ptr(), y.data_ptr(),
+                                 ws.defined() ? ws.data_ptr<float>() : nullptr, (int)M, (int)N, (int)K, (size_t)ldx,
+                                 (size_t)ldw, (size_t)lds, slabs, cur_stream()));
+  return y;
+}
+
 // y = a @ b (bf16, a [M, K] K-major, b [K, N] with unit stride along K) plus the BatchNorm
 // statistics of y per 256-row tile: {y, tiles [ceil(M / 256), N, 2] = (mean, M2)}
 std::vector<torch::Tensor> mm_bf16_bn_stats(torch::Tensor a, torch::Tensor b) {
@@ -1459,6 +1504,16 @@ void register_lm_ops(pybind11::module& m) {
         }, "the K slabs the MXFP4 linear kernel sums by default (from M, the tiles of Ns, K and the CU count, never from "
         "data): the plain call for one N, the grouped call for several, swiglu_linear_mxfp4 with swiglu=True",
         py::arg("M"), py::arg("Ns"), py::arg("K"), py::arg("swiglu") = false);
+  m.def("linear_mxfp4_gemm", &linear_mxfp4_gemm,
+        "MXFP4 weight-only GEMM for any M >= 1: x bf16 [M,K], codes uint8 [N,K/2], scales uint8 [N,K/32] -> bf16 [M,N]; "
+        "K % 128 == 0, N % 8 == 0; slabs: the runs of 128-k chunks summed in order (0: linear_mxfp4_gemm_splits(M, N, K))",
+        py::arg("x"), py::arg("codes"), py::arg("scales"), py::arg("slabs") = 0);
+  m.def("linear_mxfp4_gemm_splits", [](int64_t M, int64_t N, int64_t K) {
+          TORCH_CHECK(M >= 0 && N >= 0 && K >= 0 && M <= INT_MAX && N <= INT_MAX && K <= INT_MAX,
+                      "linear_mxfp4_gemm_splits: sizes out of range");
+          return cs_linear_mxfp4_gemm_splits((int)M, (int)N, (int)K);
+        }, "the K slabs linear_mxfp4_gemm sums for these shapes (from M, N, K and the CU count, never from data)",
+        py::arg("M"), py::arg("N"), py::arg("K"));
   m.def("mm_bf16", &mm_bf16, "C = a @ b on the bf16 matrix cores", pybind11::arg("a"), pybind11::arg("b"),
         pybind11::arg("out_f32") = false, pybind11::arg("acc") = c10::nullopt, pybind11::arg("splits") = -1);
   m.def("mm_bf16_bn_stats", &mm_bf16_bn_stats, "a @ b (bf16) plus per-256-row-tile BatchNorm (mean, M2) of the result");

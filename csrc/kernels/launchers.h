@@ -506,6 +506,32 @@ size_t cs_swiglu_linear_mxfp4_ws_floats(int M, int N, int slabs);
 hipError_t cs_swiglu_linear_mxfp4(const void* x, const void* gate, const void* gate_scales, const void* up,
                                   const void* up_scales, void* y, float* ws, int M, int N, int K, size_t ldx, size_t ldg,
                                   size_t ldgs, size_t ldu, size_t ldus, int slabs, int wgs, hipStream_t stream);
+// y[M, N] = bf16(ws[0] + ws[1] + ... + ws[slabs - 1]) for fp32 partials ws[slabs][M][N], summed in slab order:
+// linear_mxfp4_combine_kernel on a group of one, the combine of cs_linear_mxfp4 and of cs_linear_mxfp4_gemm.
+// N % 8 == 0; ws and y 16-byte aligned. M == 0 or N == 0 launches nothing.
+hipError_t cs_linear_mxfp4_combine(const float* ws, void* y, int M, int N, int slabs, hipStream_t stream);
+// The same product for any M >= 1 on an LDS-tiled matrix-core GEMM (linear_mxfp4_gemm.hip): the prefill and batches
+// over cs_linear_mxfp4_max_m() rows. Operands, K % 128 == 0 and N % 8 == 0 as for cs_linear_mxfp4; in addition the
+// scale rows are staged four bytes at a time, so lds % 4 == 0 and `scales` is 4-byte aligned (x, codes and y
+// 16-byte). K is summed in `slabs` contiguous runs of 128-k chunks, 1 <= slabs <= cs_linear_mxfp4_gemm_max_splits(K)
+// = min(K / 128, 65535), combined in slab order by cs_linear_mxfp4_combine (no atomics); ws:
+// cs_linear_mxfp4_ws_floats(M, N, slabs) floats, 16-byte aligned (may be null when slabs == 1). For a fixed `slabs`
+// the summation order of an element depends on K and `slabs` alone, so a row's bits do not depend on M or on the
+// row's position; they are not the bits of cs_linear_mxfp4.
+// Index width: the per-tile bases of x, codes, scales, y and ws are 64-bit, so each tensor may pass 2^31 bytes.
+// Inside a tile's buffer descriptor offsets are 32-bit: a tile addresses 128 rows of x, of the codes and of the
+// scales, at most 128 * ldx * 2, 128 * ldw and 128 * lds bytes, and each must stay below 0x7ffffff0 (the offset that
+// marks a row outside the operand): ldx <= cs_linear_mxfp4_gemm_max_ldx() = 8388607 elements, ldw <=
+// cs_linear_mxfp4_gemm_max_ldw() = 16777215 bytes, lds <= cs_linear_mxfp4_gemm_max_lds() = 16777215 bytes.
+// ceil(M / 128) * ceil(N / 128) <= INT_MAX. M == 0 or N == 0 launches nothing. hipErrorInvalidValue on anything else.
+int cs_linear_mxfp4_gemm_max_splits(int K);
+int64_t cs_linear_mxfp4_gemm_max_ldx();
+int64_t cs_linear_mxfp4_gemm_max_ldw();
+int64_t cs_linear_mxfp4_gemm_max_lds();
+// the default slab count: from M, N, K and the CU count only; 1 whenever the partials would pass 256 MiB
+int cs_linear_mxfp4_gemm_splits(int M, int N, int K);
+hipError_t cs_linear_mxfp4_gemm(const void* x, const void* codes, const void* scales, void* y, float* ws, int M, int N,
+                                int K, size_t ldx, size_t ldw, size_t lds, int slabs, hipStream_t stream);
 
 // decode attention against a KV cache, split over the keys (attn_decode.hip). q / o: bf16 [B, Hq, D]; kc / vc:
 // bf16 [B, Smax, Hkv, D] with row stride Hkv * D and batch stride `batch_stride` elements (% 8 == 0, so a

@@ -59,6 +59,7 @@
 // stored: an MFMA output depends on one A row and one B column only.
 #include "common.h"
 #include "launchers.h"
+#include "mxfp4_dequant_device.h"
 
 namespace {
 
@@ -91,15 +92,7 @@ struct Group {
   int G, Ntot;  // Ntot: workspace columns, the summed N
 };
 
-// the eight e2m1 codes of one dword times `scale` -> eight bf16 values in k (nibble) order
-__device__ __forceinline__ bf16x8 dequant8(unsigned d, float scale) {
-  u32x4 r;
-  r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, scale, 0));
-  r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, scale, 1));
-  r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, scale, 2));
-  r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, scale, 3));
-  return __builtin_bit_cast(bf16x8, r);
-}
+using cs::dequant8;  // mxfp4_dequant_device.h
 
 // the chunks [c0, c1) of part i when n chunks are divided as evenly as possible into parts
 __device__ __forceinline__ void even_part(int n, int parts, int i, int& c0, int& c1) {
@@ -410,6 +403,20 @@ hipError_t cs_linear_mxfp4(const void* x, const void* codes, const void* scales,
                            size_t ldx, size_t ldw, size_t lds, int slabs, int wgs, hipStream_t stream) {
   if (N == 0 && M >= 0) return hipSuccess;
   return cs_linear_mxfp4_grouped(x, &codes, &scales, &y, &N, &ldw, &lds, 1, ws, M, K, ldx, slabs, wgs, stream);
+}
+
+hipError_t cs_linear_mxfp4_combine(const float* ws, void* y, int M, int N, int slabs, hipStream_t stream) {
+  if (M == 0 || N == 0) return hipSuccess;
+  if (M < 0 || N < 0 || N % 8 != 0 || slabs < 1 || !aligned16(ws) || !aligned16(y)) return hipErrorInvalidValue;
+  const size_t quads = (size_t)M * N / 4;
+  if ((quads + 255) / 256 > 0x7fffffffu) return hipErrorInvalidValue;
+  Group grp = {};
+  grp.seg[0] = Segment{nullptr, nullptr, (__bf16*)y, 0, 0, N, 0, 0};  // a group of one: every column is its own
+  grp.G = 1;
+  grp.Ntot = N;
+  hipLaunchKernelGGL((linear_mxfp4_combine_kernel<kStore>), dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, stream,
+                     ws, grp, M, slabs);
+  return hipGetLastError();
 }
 
 hipError_t cs_swiglu_linear_mxfp4(const void* x, const void* gate, const void* gate_scales, const void* up,
